@@ -7,6 +7,12 @@ A "step" is one launch of the movegen kernel over one resident batch of 4096 syn
 all ranks (weak scaling: every rank owns its own 4096 boards; the path has no exchange step, so
 the only torch.distributed traffic is the barrier and the max-over-ranks of the elapsed time).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline needs and nothing else: corpus, W warm-up
+launches, exactly N timed launches (in up to 5 back-to-back regions; the median region is reported), the result line.
+`--full` adds every side measurement (fused id lists, four streams, saturated launch, host buffers, planes writer,
+self-play legs, training step, CPU baselines); the headline is measured the same way with and without it.
+`--dump-outputs DIR` writes what the last timed launch computed as .npy files.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -460,6 +466,8 @@ def selfplay_cpu_baseline_all_cores(sims, budget_s=10.0):
                       f"model), {sims} sims, stub evaluator (network cost excluded), per 54-ply game"}
 
 
+MIN_REGION = 500                     # launches per timed region of the headline when --steps is split (3.5 ms at 7 us a launch)
+
 ENCODE_BYTES_PER_BOARD = 16128       # 56 x 144 x 2 B planes written per board, bf16
 
 
@@ -520,6 +528,16 @@ def encode_measure(L, n=65536, steps=20):
     return out
 
 
+def dump_outputs(d, mask, count):
+    """--dump-outputs: what the last timed launch handed back -- the legal set of every board of the batch as its 66 destination
+    words (include/hive_abi.h) and the number of legal moves -- as DIR/<name>.npy.  float64 holds a 32-bit word exactly.  The
+    corpus is seeded (playout.random_positions(seed=1000 + rank)), so two builds given the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "legal_mask_words.npy"), mask.cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(d, "legal_count.npy"), count.cpu().numpy().astype(np.float64))
+
+
 def relaunch_under_torchrun(argv, gpus):
     """`python bench.py --gpus N` without a launcher: start the N ranks under torch.distributed.run as a CHILD process (this
     process has not touched the GPU yet and never will), relay rank 0's JSON line, exit with the child's code."""
@@ -541,7 +559,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--windows", type=int, default=25, help="timed regions of --steps launches each; value = their median")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement (other kernels and batch sizes, self-play, "
+                    "training, CPU baselines); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed launch (legal mask words, legal counts) as DIR/<name>.npy")
+    ap.add_argument("--windows", type=int, default=None, help="time this many regions of --steps launches EACH and report the median "
+                    "region (default: --steps launches in all, split into up to 5 regions; the fused-id-list side measurement "
+                    "of --full takes 25 regions of --steps launches unless told otherwise)")
     ap.add_argument("--boards", type=int, default=4096)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sat-boards", type=int, default=1 << 20, help="batch size of the saturated side measurement")
@@ -570,6 +594,13 @@ def main():
     ap.add_argument("--no-worker", dest="worker", action="store_false", help="skip the SelfPlayWorker (spawned producer) leg")
     ap.add_argument("--encode-boards", type=int, default=65536, help="boards per launch of the planes-writer side measurement (0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    side_windows = args.windows or 25
+    if not args.full:                            # a plain run measures the headline only: every side leg is switched off
+        args.no_cpu_baseline, args.no_overlap = True, True
+        args.sat_boards = args.encode_boards = args.selfplay_plies = args.train_steps = 0
+        args.whole_games = args.cpu_baseline_selfplay = False
 
     # ---- N ranks: either the driver started us under torch.distributed.run (RANK / WORLD_SIZE set), or we do it ourselves
     if "RANK" not in os.environ:
@@ -624,21 +655,22 @@ def main():
     for _ in range(args.warmup):
         step()
 
-    def timed_windows(fn, windows):
-        """`windows` timed regions of exactly --steps launches each, every one bracketed by barrier + synchronize on both
-        sides and timed with HIP events on the launch stream (a host clock around a 0.15 ms region mostly measures the
-        closing synchronize).  Returns per-window (device seconds, host seconds), max over ranks."""
+    def timed_windows(fn, sizes):
+        """One timed region of sizes[i] launches per entry, every one bracketed by barrier + synchronize on both sides and
+        timed with HIP events on the launch stream (a host clock around a 0.15 ms region mostly measures the closing
+        synchronize).  Returns per-region (device seconds, host seconds) scaled to --steps launches, max over ranks."""
         rows = []
-        for _ in range(windows):
+        for size in sizes:
             barrier()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
             e0.record(stream)
-            for _ in range(args.steps):
+            for _ in range(size):
                 fn()
             e1.record(stream)
             barrier()
-            rows.append((e0.elapsed_time(e1) * 1e-3, time.perf_counter() - t0))
+            k = args.steps / size
+            rows.append((e0.elapsed_time(e1) * 1e-3 * k, (time.perf_counter() - t0) * k))
         tt = torch.tensor(rows, dtype=torch.float64, device="cuda")
         if world > 1:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -646,15 +678,26 @@ def main():
 
     def spread(vals):
         v = sorted(vals)
-        return {"median": v[len(v) // 2], "min": v[0], "max": v[-1], "windows": len(v)}
+        return {"median": v[(len(v) - 1) // 2], "min": v[0], "max": v[-1], "windows": len(v)}
 
-    win = timed_windows(step, args.windows)
+    if args.windows:
+        sizes = [args.steps] * args.windows      # --windows R: R regions of --steps launches each (profile passes)
+    else:
+        # --steps launches in all, issued as up to 5 back-to-back regions of at least MIN_REGION launches: the median region
+        # leaves out the one in which the runtime grows its launch resources and any region the host was held up in, and a
+        # region's fixed cost (a few us of dispatch ramp) stays below 0.2 % of it; fewer than 3 such regions: one region
+        r = min(5, args.steps // MIN_REGION)
+        r = r if r >= 3 else 1
+        sizes = [args.steps // r + (1 if i < args.steps % r else 0) for i in range(r)]
+    win = timed_windows(step, sizes)
     dev_s = spread([w[0] for w in win])
     host_s = spread([w[1] for w in win])
-    # headline = the MEDIAN window (each window = --steps launches between two barrier + synchronize brackets, max over ranks)
+    # headline = the MEDIAN region, as the time of --steps launches (regions between two barrier + synchronize brackets, max over ranks)
     wall_max, host_wall_max = dev_s["median"], host_s["median"]
     dev_ms = wall_max * 1e3
     mean_legal = float(count.float().mean().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mask, count)
 
     t_side0 = time.perf_counter()
     selfplay = None
@@ -694,14 +737,14 @@ def main():
     # side measurement: legal set AND its compaction into sorted action ids (GamePlay.encode_action, env_hive.py:287-304)
     # -- what GamePlay.actions() returns -- by the fused launch
     with_list = None
-    if rank == 0:
+    if rank == 0 and args.full:
         lst = torch.empty((n, 256), dtype=torch.int16, device="cuda")
         lp = ctypes.c_void_p(lst.data_ptr())
         for _ in range(10):
             L.hive_movegen_launch(bp, n, mp, cp, lp, sp)
         torch.cuda.synchronize()
         lwin = []
-        for _ in range(args.windows):
+        for _ in range(side_windows):
             torch.cuda.synchronize()
             l0, l1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             l0.record(stream)
@@ -844,8 +887,11 @@ def main():
             "ms_per_step_min": round(dev_s["min"] * 1e3 / args.steps, 6),
             "ms_per_step_max": round(dev_s["max"] * 1e3 / args.steps, 6),
             "windows": dev_s["windows"],
-            "timing": "median of `windows` timed regions of exactly `steps` launches each, every region between two barrier + "
-                      "synchronize brackets, HIP events on the launch stream, max over ranks per region; min / max = the spread",
+            "timing": "`steps` launches in all, timed as `windows` back-to-back regions (`steps` launches EACH if --windows was given), "
+                      "every region between two barrier + synchronize brackets, HIP events on the launch stream, max over ranks "
+                      "per region; value / ms_per_step = the median region's time per launch, min / max = the spread",
+            "timed_steps": sum(sizes),
+            "full": args.full,
             "host_wall_ms_per_step": round(host_wall_max * 1e3 / args.steps, 6),
             "higher_is_better": True,
             "scaling": "weak",

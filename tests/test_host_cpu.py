@@ -225,7 +225,16 @@ def test_sl_schedule_host_logic():
     assert [p[4] for p in plan] == [1, 1, 2] and plan[1][3] is True
 
 
-def test_selfplay_worker_shards_games_by_global_id(tmp_path):
+@pytest.fixture
+def no_device_mask(monkeypatch):
+    """For the SelfPlayWorker tests whose stand-in children touch no GPU: they name logical GPUs 0..7, and a device mask
+    inherited from a scheduler (one entry on a one-GPU host) would only decide whether those exist.  The translation
+    through such a mask is test_selfplay_worker_device_masks_and_lost_games' subject, which sets its own."""
+    monkeypatch.delenv("HIP_VISIBLE_DEVICES", raising=False)
+    monkeypatch.delenv("CUDA_VISIBLE_DEVICES", raising=False)
+
+
+def test_selfplay_worker_shards_games_by_global_id(tmp_path, no_device_mask):
     """SURVEY 8e / woker/self_play.py:37-75,100-112: SelfPlayWorker spawns one child per GPU (HIP_VISIBLE_DEVICES set for the
     child before it starts), hands rank r the contiguous shard of the global game ids, gathers the finished games, prints
     the progress line every 10 games and flushes rows every N games.  With a GPU-free stand-in worker at world size 2:
@@ -406,7 +415,7 @@ def test_packed_game_batches_round_trip_slice_and_concat(tmp_path):
     assert np.array_equal(records.packed_values(packed), records.dataset_from_games(games)[2])
 
 
-def test_selfplay_worker_takes_packed_batches_from_two_ranks(tmp_path):
+def test_selfplay_worker_takes_packed_batches_from_two_ranks(tmp_path, no_device_mask):
     """The compact route at world size 2 without a GPU: children send packed batches of several games per message
     (records.pack_games' arrays); the parent cuts files at exactly games_per_file games on writer threads, `results` is a
     lazy game-id mapping, and files + mapping hold every game exactly as fabricated."""
@@ -430,7 +439,7 @@ def test_selfplay_worker_takes_packed_batches_from_two_ranks(tmp_path):
                 assert all(np.array_equal(np.asarray(u), np.asarray(v)) for u, v in zip(x, y))
 
 
-def test_selfplay_worker_parent_keeps_up_with_eight_ranks_of_real_size_waves(tmp_path):
+def test_selfplay_worker_parent_keeps_up_with_eight_ranks_of_real_size_waves(tmp_path, no_device_mask):
     """The ONE serial point of the 8-GPU producer (woker/self_play.py:37-75,100-112: one parent gathers every game and writes
     the files): eight ranks hand over real-size lock-step waves -- 1024 games = 55 k rows = ~90 MB per message, as
     mcts.SelfPlay.drain_finished_packed sends them -- at 8 x 4,700 games/min (one wave per rank every 13 s, all ranks at the
@@ -444,6 +453,8 @@ def test_selfplay_worker_parent_keeps_up_with_eight_ranks_of_real_size_waves(tmp
     waves = int(os.environ.get("HIVE_SOAK_PARENT_WAVES", "2"))
     period_s = per_wave / 4700.0 * 60.0                        # 13.07 s: one GPU's wave period at 4,700 games/min
     total = ranks * per_wave * waves
+    spool = os.environ.get("HIVE_SPOOL_DIR", "/dev/shm")       # shared with other runs on the host: only this run's files count
+    parked_before = {f for f in os.listdir(spool) if f.startswith("hive_wave_")}
     w = SelfPlayWorker(total_games=total, games_per_gpu=per_wave, sims=1, gpus=list(range(ranks)), seed=5,
                        slots=int(period_s * 1000), datapath=str(tmp_path), games_per_file=256, report_every=0,
                        worker=fk.soak_worker, log=lambda *_: None, row_format="compact", keep_results=False)
@@ -456,7 +467,7 @@ def test_selfplay_worker_parent_keeps_up_with_eight_ranks_of_real_size_waves(tmp
     assert res.rows_of(total - 1) == 54                         # keep_results=False: ids and lengths stay, the rows are in the files
     with pytest.raises(KeyError):
         res[0]
-    assert not [f for f in os.listdir(os.environ.get("HIVE_SPOOL_DIR", "/dev/shm")) if f.startswith("hive_wave_")]   # nothing left parked
+    assert not [f for f in os.listdir(spool) if f.startswith("hive_wave_") and f not in parked_before]   # nothing left parked
     # the rate the parent sustained from the ranks' "ready" to the last flushed file
     rate = total / (t1 - min(w.ready_at.values())) * 60.0
     st = w.parent_stats
