@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "hive_search_node_counts", "hive_search_set_transpositions", "hive_search_transposition_hits",
     "hive_search_set_game_ids", "hive_search_root_stats", "hive_search_leaf_histogram", "hive_search_sample_noise",
     "hive_search_leaf_need",
+    "hive_arena_split_launch", "hive_arena_join_launch", "hive_arena_opening_launch", "hive_arena_score_launch",
     # include/hive_nn.h
     "hive_nn_conv3x3", "hive_nn_resblock", "hive_nn_conv3x3_dt", "hive_nn_resblock_dt", "hive_nn_tower",
     "hive_nn_conv3x3_sel", "hive_nn_resblock_sel", "hive_nn_copy_rows", "hive_nn_tower72", "hive_nn_compact_rows", "hive_nn_tower72_balanced", "hive_nn_tower72_plan_bytes", "hive_nn_conv72", "hive_nn_conv72_add", "hive_nn_conv72_stats",
@@ -130,6 +131,10 @@ def load():
     L.hive_nn_conv3x3_sel.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     L.hive_nn_resblock_sel.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
     L.hive_search_leaf_need.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.hive_arena_split_launch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.hive_arena_join_launch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.hive_arena_opening_launch.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_uint64, i32, vp, vp]
+    L.hive_arena_score_launch.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.hive_nn_copy_rows.argtypes = [vp, vp, i32, ctypes.c_longlong, vp]
     L.hive_nn_tower72.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.hive_nn_compact_rows.argtypes = [vp, i32, vp, vp, vp]

@@ -134,6 +134,35 @@ class TreeSearch:
         check(self.L.hive_search_set_stream(self._h, s))
         return s
 
+    def _evaluate(self, k, n, s):
+        """The network's (p, v) for the n = k * games leaves of this round of simulations (rows the backup never reads,
+        and duplicates of an evaluated row, are switched off for an evaluator that takes the flags)."""
+        L = self.L
+        if self.skip_unread_rows:
+            check(L.hive_search_leaf_need(self._h, k, _p(self.leaf_boards), _p(self.leaf_over), _p(self.leaf_need),
+                                          _p(self.evals_run)))
+            if self.share_equal_leaves:
+                check(L.hive_leaf_dedup_launch(_p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.leaf_need),
+                                               _p(self.leaf_rep), _p(self.leaf_keys), _p(self.evals_run), s))
+                if self._store is not None:
+                    if getattr(self.evaluator, "weights_version", 0) != self._store_version:      # new weights: old answers are void
+                        check(L.hive_leaf_store_clear(self._store, s))
+                        self._store_version = getattr(self.evaluator, "weights_version", 0)
+                    check(L.hive_leaf_store_lookup(self._store, _p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.leaf_keys),
+                                                   _p(self.leaf_need), _p(self.leaf_hit), _p(self.evals_run), s))
+                p, v = self.evaluator(self.planes[:n], need=self.leaf_need[:n], rep=self.leaf_rep[:n])
+                if self._store is not None:
+                    p = p.float().contiguous()
+                    v = v.float().contiguous().view(-1)
+                    check(L.hive_leaf_store_update(self._store, _p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.leaf_keys),
+                                                   _p(self.leaf_need), _p(self.leaf_rep), _p(self.leaf_hit), _p(p), _p(v), s))
+            else:
+                p, v = self.evaluator(self.planes[:n], need=self.leaf_need[:n])
+        else:
+            p, v = self.evaluator(self.planes[:n])
+        self.evals_launched += n
+        return p, v
+
     def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False):
         """-> (action int32[games] (-1 pass, -2 inactive/terminal root), policy fp32[games,1584], sum_n int32[games])"""
         L, G = self.L, self.games
@@ -151,29 +180,7 @@ class TreeSearch:
                                      _p(self.leaf_over), _p(self.leaf_winner), s))
             if first and keep_root_planes:
                 self.root_planes = self.workspace[:G * 144].clone()
-            if self.skip_unread_rows:
-                check(L.hive_search_leaf_need(self._h, k, _p(self.leaf_boards), _p(self.leaf_over), _p(self.leaf_need),
-                                              _p(self.evals_run)))
-                if self.share_equal_leaves:
-                    check(L.hive_leaf_dedup_launch(_p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.leaf_need),
-                                                   _p(self.leaf_rep), _p(self.leaf_keys), _p(self.evals_run), s))
-                    if self._store is not None:
-                        if getattr(self.evaluator, "weights_version", 0) != self._store_version:      # new weights: old answers are void
-                            check(L.hive_leaf_store_clear(self._store, s))
-                            self._store_version = getattr(self.evaluator, "weights_version", 0)
-                        check(L.hive_leaf_store_lookup(self._store, _p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.leaf_keys),
-                                                       _p(self.leaf_need), _p(self.leaf_hit), _p(self.evals_run), s))
-                    p, v = self.evaluator(self.planes[:n], need=self.leaf_need[:n], rep=self.leaf_rep[:n])
-                    if self._store is not None:
-                        p = p.float().contiguous()
-                        v = v.float().contiguous().view(-1)
-                        check(L.hive_leaf_store_update(self._store, _p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.leaf_keys),
-                                                       _p(self.leaf_need), _p(self.leaf_rep), _p(self.leaf_hit), _p(p), _p(v), s))
-                else:
-                    p, v = self.evaluator(self.planes[:n], need=self.leaf_need[:n])
-            else:
-                p, v = self.evaluator(self.planes[:n])
-            self.evals_launched += n
+            p, v = self._evaluate(k, n, s)
             p = p.float().contiguous()
             v = v.float().contiguous().view(-1)
             for sl in range(k):
@@ -219,6 +226,78 @@ class TreeSearch:
         self._stream()
         check(self.L.hive_search_transposition_hits(self._h, _p(out)))
         return out
+
+
+class ArenaSearch(TreeSearch):
+    """TreeSearch whose games are searched by TWO networks (woker/evaluation.py: one HivePlayer per side, each with its own
+    model): the search of game g is the thinking of the side to move at its root, so all its leaves go to network A iff
+    a_white[g] == (root turn is odd), else to network B.  a_white = device int8[games], read at every search (the caller
+    may rewrite it in place between searches).  Both networks see the same leaf batch with their own row flags
+    (hive_arena_split_launch): a tower costs what its own rows cost; equal leaves are shared within a network, never
+    across.  hive_arena_join_launch merges the two predictions for the backup.
+
+    An evaluator without `accepts_need` (a stub, the library path) gets the whole batch.  `rows_evaluated()` = the rows
+    each network evaluated; `evals_run` is their sum.  reuse_store is refused: the store's key does not hold the network."""
+
+    def __init__(self, games, sims, evaluator_a, evaluator_b, a_white, device=None, slots=1, seed=0, plane_dtype=None,
+                 **options):
+        if options.get("reuse_store"):
+            raise ValueError("ArenaSearch: reuse_store keeps evaluations by position alone, not by network")
+        super().__init__(games, sims, evaluator_a, device, slots, seed, plane_dtype, **options)
+        self.evaluator_a, self.evaluator_b = evaluator_a, evaluator_b
+        assert a_white.dtype == torch.int8 and a_white.numel() == games and a_white.is_cuda and a_white.is_contiguous()
+        self.a_white = a_white
+        n, dev = games * slots, self.device
+        skip, share = bool(options.get("skip_unread_rows", True)), bool(options.get("share_equal_leaves", True))
+        self._nets = []
+        for k, e in enumerate((evaluator_a, evaluator_b)):
+            flags = skip and bool(getattr(e, "accepts_need", False))
+            self._nets.append({
+                "evaluator": e, "flags": flags,
+                "share": flags and share and n <= 4096 and bool(getattr(e, "accepts_rep", False)),
+                "need": torch.ones((n,), dtype=torch.int8, device=dev),
+                "rep": torch.arange(n, dtype=torch.int32, device=dev),
+                "keys": torch.zeros((n,), dtype=torch.int64, device=dev)})
+        self.rows = torch.zeros((2,), dtype=torch.int64, device=dev)        # rows evaluated by A, by B
+        self._roots = None
+
+    def rows_evaluated(self):
+        """(rows network A evaluated, rows network B evaluated) since create."""
+        a, b = self.rows.cpu().tolist()
+        return int(a), int(b)
+
+    def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False):
+        self._roots = root_boards
+        out = super().search(root_boards, root_hist, active, selfplay, keep_root_planes)
+        torch.sum(self.rows, 0, keepdim=True, out=self.evals_run)
+        return out
+
+    def _evaluate(self, k, n, s):
+        L, A, B = self.L, self._nets[0], self._nets[1]
+        check(L.hive_search_leaf_need(self._h, k, _p(self.leaf_boards), _p(self.leaf_over), _p(self.leaf_need), None))
+        counters = [ctypes.c_void_p(self.rows.data_ptr() + 8 * i) if net["flags"] else None for i, net in enumerate(self._nets)]
+        check(L.hive_arena_split_launch(_p(self._roots), _p(self.a_white), _p(self.leaf_need), self.games, k,
+                                        _p(A["need"]), _p(B["need"]), counters[0], counters[1], s))
+        for net, counter in zip(self._nets, counters):
+            if net["share"]:
+                check(L.hive_leaf_dedup_launch(_p(self.leaf_boards), _p(self.leaf_hist), n, _p(net["need"]), _p(net["rep"]),
+                                               _p(net["keys"]), counter, s))
+        out = []
+        for i, net in enumerate(self._nets):
+            if net["share"]:
+                p, v = net["evaluator"](self.planes[:n], need=net["need"][:n], rep=net["rep"][:n])
+            elif net["flags"]:
+                p, v = net["evaluator"](self.planes[:n], need=net["need"][:n])
+            else:
+                p, v = net["evaluator"](self.planes[:n])
+                self.rows[i] += n
+            out.append((p.float().contiguous(), v.float().contiguous().view(-1)))
+        (p, v), (pb, vb) = out
+        if p.data_ptr() == pb.data_ptr():        # (an evaluator that hands out one static buffer, called twice)
+            raise _lib.HiveError(-1, "ArenaSearch: the two evaluators returned the same output buffer")
+        check(L.hive_arena_join_launch(_p(self._roots), _p(self.a_white), self.games, k, _p(p), _p(v), _p(pb), _p(vb), s))
+        self.evals_launched += n
+        return p, v
 
 
 class SelfPlay:

@@ -130,6 +130,41 @@ int hive_search_leaf_histogram(HiveSearch *s, int32_t *hist);
 int hive_search_sample_noise(uint64_t seed, int64_t first_game, int turn, float alpha, int k, int draws, const float *prior,
                              float eps, float *out, void *stream);
 
+/* ---- Arena: two networks play each other (woker/evaluation.py:40-111,128-310), both searched in ONE lock-step batch.
+ *
+ * A game is played by network A on one colour and network B on the other: a_white = int8[games], 1 = A is white.  A search
+ * is the thinking of the side to move at its ROOT, so every leaf row of game g (rows are laid out slot * games + g, as
+ * hive_search_select / hive_search_backup take them) belongs to network A iff a_white[g] == (root turn is odd); odd turn =
+ * white to move (HiveBoard.turn).  All pointers are device pointers; stream = hipStream_t. */
+
+/* need (int8[slots * games] of hive_search_leaf_need; NULL = all ones) split by owner:
+ * need_a[r] = need[r] & owner_is_a, need_b[r] = need[r] & !owner_is_a.  rows_a / rows_b (either may be NULL): uint64
+ * device counters, the number of rows flagged is ADDED to them. */
+int hive_arena_split_launch(const HiveBoard *root_boards, const int8_t *a_white, const int8_t *need, int games, int slots,
+                            int8_t *need_a, int8_t *need_b, uint64_t *rows_a, uint64_t *rows_b, void *stream);
+
+/* In place: the rows B owns take B's prediction, p_a[r][0..1583] = p_b[r][..] and v_a[r] = v_b[r]; A's own rows are
+ * untouched.  p = float[slots * games][1584], 16-byte aligned; v = float[slots * games]. */
+int hive_arena_join_launch(const HiveBoard *root_boards, const int8_t *a_white, int games, int slots, float *p_a, float *v_a,
+                           const float *p_b, const float *v_b, void *stream);
+
+/* The uniformly random opening (evaluation.py:169,187 play random moves while turn <= 4): for every active game
+ * (active = int8[n] or NULL) whose turn is <= opening_turns, action[g] = list[g][idx], or -1 (pass) when count[g] == 0;
+ * idx = ((r >> 32) * count[g]) >> 32 with r = the first 64 bits of the search's counter-based generator keyed on
+ * (seed, pair_id[g], turn, 0) and nothing else: both games of a pair, in any slot of any batch, get the same opening.
+ * count = int32[n], list = int16[n][HIVE_LIST_CAP] ascending ids (hive_batch_legal), pair_id = int64[n].  Other entries of
+ * action (int32[n]) are left alone. */
+int hive_arena_opening_launch(const HiveBoard *boards, const int32_t *count, const int16_t *list, const int64_t *pair_id,
+                              const int8_t *active, int n, uint64_t seed, int opening_turns, int32_t *action, void *stream);
+
+/* Scores every active game (active = int8[n] or NULL) that is over or has reached the length cap (over / winner as
+ * hive_batch_terminal: winner 1 white, 2 black, 0 none): result[g] (int8[n]) = 1 A won, 2 B won, 3 draw (both queens
+ * surrounded), 4 length cap (turn >= max_game_length, game not over); 0 for every other game.  tally = int32[8], ADDED to:
+ * [0] A wins as white [1] A wins as black [2] B wins as white [3] B wins as black [4] draws [5] length caps
+ * [6] finished games [7] sum of their final turn numbers. */
+int hive_arena_score_launch(const HiveBoard *boards, const int8_t *over, const int8_t *winner, const int8_t *active,
+                            const int8_t *a_white, int n, int max_game_length, int8_t *result, int32_t *tally, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

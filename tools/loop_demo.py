@@ -2,12 +2,19 @@
 reload the weights): GPU self-play with packed per-ply records -> the trainer's tensors widened ON THE GPU from the packed
 features (records.dataset_tensors_gpu_packed: the same planes, policies and 0.99 ** k discounted values optimize.py:42-65
 builds from the reference's JSON rows; that equivalence is what tests/test_gpu_scale.py and tests/test_host_cpu.py check)
--> Trainer steps on the same ChessNet -> InferenceNet.refresh -> next round of self-play.  Sized to run in well under a minute."""
-import os, sys, time, numpy as np, torch
+-> Trainer steps on the same ChessNet -> InferenceNet.refresh -> next round of self-play.  Sized to run in well under a minute.
+
+--gate PAIRS (default 0 = off): after training, the trained network plays PAIRS pairs of arena games (arena.Arena) against
+the network the round started from, and the self-play evaluator is refreshed only if it passes AlphaZero's gate
+(ArenaResult.passes(): score >= 0.55)."""
+import argparse, os, sys, time, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hive_alphazero_amd import mcts, records
 from hive_alphazero_amd.alpha_net import ChessNet, InferenceNet, Trainer
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--gate", type=int, default=0, metavar="PAIRS", help="arena pairs that gate the refresh (0 = refresh always)")
+gate = ap.parse_args().gate
 games, sims, rounds = 256, 16, 2
 torch.manual_seed(0)
 net = ChessNet().cuda()
@@ -44,7 +51,18 @@ for rnd in range(rounds):
     trainer.end_epoch()
     torch.cuda.synchronize()
     t_tr = time.perf_counter() - t0
-    evaluator.refresh(net)
+    if gate > 0:
+        from hive_alphazero_amd.arena import Arena
+        candidate = InferenceNet(net.eval(), dtype=evaluator.dtype)
+        match = Arena(candidate, evaluator, pairs=gate, sims=sims, seed=1000 + rnd)
+        verdict = match.run()
+        assert match.illegal_count() == 0
+        match.close()
+        print(f"round {rnd}: gate {verdict!r} -> {'refresh' if verdict.passes() else 'keep the old weights'}", flush=True)
+        if verdict.passes():
+            evaluator.refresh(net)
+    else:
+        evaluator.refresh(net)
     print(f"round {rnd}: {sp.plies} plies of {games} games x {sims} sims in {t_sp:.1f} s, W/B/draw {results}, illegal {illegal}; "
           f"{n} rows of {records.packed_games(packed)} games widened on the GPU in {t_ds * 1e3:.0f} ms; "
           f"20 training steps of 512 in {t_tr:.1f} s, loss {losses[0]:.3f} -> {losses[-1]:.3f}", flush=True)
