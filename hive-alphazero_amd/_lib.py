@@ -34,6 +34,8 @@ ABI_SYMBOLS = [
     "hive_single_create", "hive_single_destroy", "hive_single_advance", "hive_single_encode",
     "hive_leaf_store_create", "hive_leaf_store_destroy", "hive_leaf_store_clear", "hive_leaf_store_lookup", "hive_leaf_store_update",
     "hive_leaf_store_stats",
+    "hive_replay_create", "hive_replay_destroy", "hive_replay_clear", "hive_replay_stats", "hive_replay_append",
+    "hive_replay_import", "hive_replay_export", "hive_replay_sample",
     # include/hive_search.h
     "hive_search_create", "hive_search_destroy", "hive_search_set_stream", "hive_search_set_params",
     "hive_search_set_roots", "hive_search_select", "hive_search_backup", "hive_search_policy",
@@ -156,6 +158,15 @@ def load():
     L.hive_leaf_store_update.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.hive_leaf_store_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     f32, i64 = ctypes.c_float, ctypes.c_longlong
+    p64, u64 = ctypes.POINTER(ctypes.c_int64), ctypes.c_uint64
+    L.hive_replay_create.argtypes = [i32, ctypes.c_int64, vp, ctypes.POINTER(vp)]
+    L.hive_replay_destroy.argtypes = [vp]
+    L.hive_replay_clear.argtypes = [vp, vp]
+    L.hive_replay_stats.argtypes = [vp, p64, p64, p64]
+    L.hive_replay_append.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, vp]
+    L.hive_replay_import.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
+    L.hive_replay_export.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hive_replay_sample.argtypes = [vp, vp, u64, u64, u64, i32, i32, i32, vp, vp, vp, vp, vp]
     L.hive_nn_bn_workspace_floats.restype = i32
     L.hive_nn_bn_act_fwd.argtypes = [vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i64, i32, i32, vp]
     L.hive_nn_bn_act_fwd_partial.argtypes = [vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, i32, i64, i32, vp]

@@ -31,6 +31,7 @@
 #include "hive_bb.hpp"
 #include "hive_tables.hpp"
 #include "hive_step.hpp"
+#include "hive_planes.hpp"      // PlaneVal, plane_store_board: the store half of hive_expand_kernel
 
 namespace hive {
 
@@ -861,40 +862,6 @@ hive_list_kernel(const uint32_t *__restrict__ mask, int n, int16_t *__restrict__
     emit_id_list(dest[wv], any[wv], cells[wv], rowbuf[wv], list + b * HIVE_LIST_CAP, lane);
 }
 
-// value encoders for the plane writer
-template <typename T> struct PlaneVal;
-template <> struct PlaneVal<float> {
-    static __device__ __forceinline__ uint32_t one() { return 0x3F800000u; }
-    static __device__ __forceinline__ uint32_t of(unsigned v) { return __float_as_uint((float)v); }
-};
-struct half_tag {};
-struct bf16_tag {};
-template <> struct PlaneVal<half_tag> {
-    static __device__ __forceinline__ uint32_t one() { return 0x3C00u; }
-    static __device__ __forceinline__ uint32_t of(unsigned v)
-    {
-        _Float16 hval = (_Float16)(float)v;
-        return (uint32_t) __builtin_bit_cast(unsigned short, hval);
-    }
-};
-template <> struct PlaneVal<bf16_tag> {
-    static __device__ __forceinline__ uint32_t one() { return 0x3F80u; }
-    static __device__ __forceinline__ uint32_t of(unsigned v) { return __float_as_uint((float)v) >> 16; }   // v <= 255: exact
-};
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// NT: streaming (nontemporal) stores for launches whose output is far larger than the caches -- 5.3 instead of 4.2 TB/s at
-// 65,536 boards (1 GB of planes); leaf batches of a search (<= 4096 boards, read back at once by the network) keep plain stores
-template <bool NT>
-__device__ __forceinline__ void plane_store(u32x4 val, u32x4 *ptr)
-{
-    if (NT) __builtin_nontemporal_store(val, ptr);
-    else *ptr = val;
-}
-constexpr int kExpandStreamBoards = 8192;              // from this many boards per launch (127 MB of bf16 planes) on: NT stores
-constexpr int kExpandAhead = 4;                        // boards whose inputs are in flight per workgroup
-constexpr long long kExpandMaxBlocks = 256 * 8;       // all resident at once: 8 workgroups of 4 waves per CU
-
 // Packed features (56 bits per cell) + history boards + turn -> the plane tensor (GamePlay.encode_board's output,
 // env_hive.py:320-447); pure streaming-store kernel.  A workgroup takes whole boards (grid-stride).  Per board: 144
 // threads complete the cells' 56-bit words in LDS (packed features | the eight history bits of planes 36..43, read from
@@ -906,8 +873,7 @@ __global__ void __launch_bounds__(256)
 hive_expand_kernel(const HiveBoard *__restrict__ boards, const HiveHistory *__restrict__ hist,
                    const unsigned long long *__restrict__ feat, int n, void *__restrict__ planes)
 {
-    using V = typename std::conditional<DT == 0, float, typename std::conditional<DT == 1, half_tag, bf16_tag>::type>::type;
-    constexpr int kItems = kCells * HIVE_PLANES / 8;      // 1008 items of 8 elements per board = 4 x 252
+    using V = PlaneType<DT>;
     __shared__ unsigned long long full[2][kCells];
     const uint32_t one = PlaneVal<V>::one();
     const int tid = threadIdx.x;
@@ -953,33 +919,7 @@ hive_expand_kernel(const HiveBoard *__restrict__ boards, const HiveHistory *__re
         // (the other buffer is rewritten only after the NEXT barrier: no second one needed; a raw barrier behind an
         // LDS-only wait, because __syncthreads() would also wait for the previous board's stores to be acknowledged)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        {
-            // items tid, tid + 256, tid + 512, tid + 768 (< 1008): every wave's store is one 128-byte-aligned KiB
-            HIVE_UNROLL for (int j = 0; j < 4; ++j) {
-                if (j == 3 && tid >= kItems - 768) break;
-                const int e0 = (tid + j * 256) * 8;
-                uint32_t v[8];
-                if (LAYOUT == HIVE_HWC) {
-                    const int cell = e0 / HIVE_PLANES, p0 = e0 - cell * HIVE_PLANES;
-                    const unsigned bits8 = (unsigned)(full[buf][cell] >> p0) & 0xFFu;
-                    HIVE_UNROLL for (int k = 0; k < 8; ++k) v[k] = ((bits8 >> k) & 1u) ? one : 0u;
-                    if (p0 == 24) v[7] = tv;      // plane 31 = raw turn number (env_hive.py:331)
-                } else {
-                    const int pl = e0 / kCells, c0 = e0 - pl * kCells;
-                    HIVE_UNROLL for (int k = 0; k < 8; ++k) v[k] = ((full[buf][c0 + k] >> pl) & 1ull) ? one : 0u;
-                    if (pl == 31) { HIVE_UNROLL for (int k = 0; k < 8; ++k) v[k] = tv; }
-                }
-                const long long eoff = b * (long long)(kCells * HIVE_PLANES) + e0;
-                if (DT == 0) {
-                    u32x4 *dst = reinterpret_cast<u32x4 *>(reinterpret_cast<float *>(planes) + eoff);
-                    plane_store<NT>(u32x4{v[0], v[1], v[2], v[3]}, dst);
-                    plane_store<NT>(u32x4{v[4], v[5], v[6], v[7]}, dst + 1);
-                } else {
-                    u32x4 *dst = reinterpret_cast<u32x4 *>(reinterpret_cast<uint16_t *>(planes) + eoff);
-                    plane_store<NT>(u32x4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)}, dst);
-                }
-            }
-        }
+        plane_store_board<DT, LAYOUT, NT>(full[buf], one, tv, planes, b, tid);
     }
 }
 

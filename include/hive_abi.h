@@ -206,6 +206,47 @@ int hive_leaf_store_update(HiveLeafStore *s, const HiveBoard *boards, const Hive
                            const int8_t *need, const int32_t *rep, const int32_t *hit, float *p, float *v, void *stream);
 int hive_leaf_store_stats(HiveLeafStore *s, uint64_t *served, uint64_t *inserted);   /* synchronises */
 
+/* ---- The replay window: the most recent `capacity` self-play rows, kept packed in HBM, and the minibatch drawn from
+ * them in one launch.  A ring of row slots, structure-of-arrays (about 2.9 KB per row): feat u64[144], the mover's history
+ * words u32[4][2][6], (valid history entries, turn, mover) bytes, the training value f32, and the visit policy as a count
+ * plus idx i16[HIVE_LIST_CAP] and val f32[HIVE_LIST_CAP].  The write position and the live count are kept on the host;
+ * only stats and export wait for the device.  Not thread-safe; one stream at a time.
+ *   create  discount = HOST f32[256], discount[k] = what a value is multiplied by when its side still has k moves to come
+ *           (NULL: 0.99 ** k computed in double and rounded to float)
+ *   append  DEVICE pointers to one packed batch (the arrays of a play_<ts>.npz: feat u64[rows][144], hist u32[rows][48],
+ *           meta u8[rows][3], pol_idx i16 / pol_val f32 in CSR form under pol_ptr i64[rows + 1], game_ptr i64[games + 1],
+ *           game_val i8[games] = the result from white's side) plus pol_ptr_host, the HOST copy of pol_ptr, which is
+ *           checked before anything is written: a row with more than HIVE_LIST_CAP entries is HIVE_E_ARG.  Row i goes to
+ *           slot (head + i) mod capacity -- a batch longer than the ring keeps its last `capacity` rows -- with its policy
+ *           in the fixed-width form and its value computed from its WHOLE game: the mover's side of game_val (0 = draw or
+ *           length cap: -1 for both sides) times discount[later moves of the same side in that game].
+ *   import  the same for rows in the form export returns (values and fixed-width policies as stored)
+ *   export  the live rows, oldest first, into DEVICE arrays: feat u64[live][144], hist u32[live][48], meta u8[live][4]
+ *           (the fourth byte is 0), pol_cnt i32[live], pol_idx i16[live][HIVE_LIST_CAP], pol_val f32[live][HIVE_LIST_CAP],
+ *           values f32[live]; any of them may be NULL.  Synchronises.
+ *   sample  one launch -> a minibatch of n rows: planes [n][12][12][56] or [n][56][12][12] of `dtype` exactly as
+ *           hive_expand_launch writes them, policies f32[n][1584], values f32[n].  indices = DEVICE i64[n] of logical row
+ *           numbers (0 = the oldest live row; a number outside [0, live) is clamped into it), or NULL: entry i is then
+ *           drawn on the device as a pure function of (seed, step, stream_id, i, live) -- the high half of
+ *           (x >> 32) * live, x the first output of the counter-based generator keyed by (seed, step, stream_id, i) --
+ *           and written to indices_out (DEVICE i64[n], may be NULL).  Duplicates are legal; every output byte is written.
+ *           The outputs must be 16-byte aligned.  An empty window is HIVE_E_STATE. */
+typedef struct HiveReplay HiveReplay;
+int hive_replay_create(int device, int64_t capacity, const float *discount, HiveReplay **out);
+int hive_replay_destroy(HiveReplay *r);
+int hive_replay_clear(HiveReplay *r, void *stream);
+int hive_replay_stats(HiveReplay *r, int64_t *live, int64_t *appended, int64_t *capacity);
+int hive_replay_append(HiveReplay *r, const uint64_t *feat, const uint32_t *hist, const uint8_t *meta, const int16_t *pol_idx,
+                       const float *pol_val, const int64_t *pol_ptr, const int64_t *game_ptr, const int8_t *game_val,
+                       const int64_t *pol_ptr_host, int64_t rows, int64_t games, void *stream);
+int hive_replay_import(HiveReplay *r, const uint64_t *feat, const uint32_t *hist, const uint8_t *meta, const int32_t *pol_cnt,
+                       const int16_t *pol_idx, const float *pol_val, const float *values, int64_t rows, void *stream);
+int hive_replay_export(HiveReplay *r, uint64_t *feat, uint32_t *hist, uint8_t *meta, int32_t *pol_cnt, int16_t *pol_idx,
+                       float *pol_val, float *values, void *stream);
+int hive_replay_sample(HiveReplay *r, const int64_t *indices, uint64_t seed, uint64_t step, uint64_t stream_id, int n,
+                       HiveDType dtype, HiveLayout layout, void *planes, float *policies, float *values, int64_t *indices_out,
+                       void *stream);
+
 /* ---- One position, HOST buffers: the single-game surface of GamePlay without a round trip per question.
  * A HiveSingle owns a stream, a device block and a pinned host mirror; a call copies the position in, runs its kernels
  * as one launch chain, copies the answers out and synchronises once.  Not thread-safe; distinct handles are independent

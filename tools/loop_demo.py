@@ -6,7 +6,11 @@ builds from the reference's JSON rows; that equivalence is what tests/test_gpu_s
 
 --gate PAIRS (default 0 = off): after training, the trained network plays PAIRS pairs of arena games (arena.Arena) against
 the network the round started from, and the self-play evaluator is refreshed only if it passes AlphaZero's gate
-(ArenaResult.passes(): score >= 0.55)."""
+(ArenaResult.passes(): score >= 0.55).
+
+--replay ROWS (default 0 = train on the round's own rows, as above): the rounds share one replay.ReplayBuffer of ROWS rows
+on the GPU; every round appends its packed batches (1.5 KB per row go up, nothing is widened ahead of time) and the 20
+training steps draw their minibatches from the whole window with buf.sample(512, step=...) -- one launch per minibatch."""
 import argparse, os, sys, time, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hive_alphazero_amd import mcts, records
@@ -14,7 +18,13 @@ from hive_alphazero_amd.alpha_net import ChessNet, InferenceNet, Trainer
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--gate", type=int, default=0, metavar="PAIRS", help="arena pairs that gate the refresh (0 = refresh always)")
-gate = ap.parse_args().gate
+ap.add_argument("--replay", type=int, default=0, metavar="ROWS", help="train from a replay window of ROWS rows shared by the rounds (0 = off)")
+opts = ap.parse_args()
+gate, window = opts.gate, opts.replay
+buf = None
+if window > 0:
+    from hive_alphazero_amd.replay import ReplayBuffer
+    buf = ReplayBuffer(window)
 games, sims, rounds = 256, 16, 2
 torch.manual_seed(0)
 net = ChessNet().cuda()
@@ -38,14 +48,22 @@ for rnd in range(rounds):
     sp.close()
     packed = records.concat_packed(batches)
     t0 = time.perf_counter()
-    states, policies, values = records.dataset_tensors_gpu_packed(packed, dtype=torch.float32, layout="chw")
+    if buf is not None:
+        for b in batches:
+            buf.add_packed(b)
+        n = len(packed["meta"])
+    else:
+        states, policies, values = records.dataset_tensors_gpu_packed(packed, dtype=torch.float32, layout="chw")
+        n = states.shape[0]
     torch.cuda.synchronize()
     t_ds = time.perf_counter() - t0
-    n = states.shape[0]
     t0 = time.perf_counter()
     losses = []
     g = torch.Generator(device="cuda").manual_seed(rnd)
-    for _ in range(20):
+    for k in range(20):
+        if buf is not None:
+            losses.append(trainer.step(*buf.sample(512, step=rnd * 20 + k, layout="nchw_channels_last")))
+            continue
         idx = torch.randint(0, n, (min(512, n),), generator=g, device="cuda")
         losses.append(trainer.step(states[idx], policies[idx], values[idx]))
     trainer.end_epoch()
@@ -64,7 +82,9 @@ for rnd in range(rounds):
     else:
         evaluator.refresh(net)
     print(f"round {rnd}: {sp.plies} plies of {games} games x {sims} sims in {t_sp:.1f} s, W/B/draw {results}, illegal {illegal}; "
-          f"{n} rows of {records.packed_games(packed)} games widened on the GPU in {t_ds * 1e3:.0f} ms; "
+          + (f"{n} rows of {records.packed_games(packed)} games widened on the GPU in {t_ds * 1e3:.0f} ms; " if buf is None else
+             f"{n} rows of {records.packed_games(packed)} games appended to the replay window in {t_ds * 1e3:.0f} ms "
+             f"(fill {len(buf)} / {buf.capacity} rows, {buf.rows_seen} seen); ") +
           f"20 training steps of 512 in {t_tr:.1f} s, loss {losses[0]:.3f} -> {losses[-1]:.3f}", flush=True)
     assert illegal == 0 and all(np.isfinite(l) for l in losses) and records.packed_games(packed) == games
 print("ok")
