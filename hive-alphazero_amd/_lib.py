@@ -185,3 +185,21 @@ def load():
 def check(rc):
     if rc != 0:
         raise HiveError(rc, load().hive_last_error().decode())
+
+
+# ---- torch tensors, streams and dtypes as the ABI takes them (torch is imported inside: this module loads without it)
+def ptr(t):
+    """A tensor's device address as the ABI's pointer argument (None stays None: an optional argument left out)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def stream_ptr(device):
+    """The current torch stream of `device` as the ABI's hipStream_t argument."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def dtype_code(dtype):
+    """torch dtype -> HiveDType (include/hive_abi.h); KeyError for anything but fp32 / fp16 / bf16."""
+    import torch
+    return {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}[dtype]

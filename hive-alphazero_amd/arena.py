@@ -14,6 +14,7 @@ The statistics (`pair_scores`, `score_interval`, `elo`, `ArenaResult`) are plain
 import ctypes
 import math
 
+from ._lib import ptr as _p, stream_ptr
 from .config import MAX_GAME_LENGTH
 
 A_WIN, B_WIN, DRAW, CAP = 1, 2, 3, 4                 # result codes of hive_arena_score_launch
@@ -129,10 +130,6 @@ class ArenaResult:
 
 
 # ---------------------------------------------------------------------------------------- the engine
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class Arena:
     """`pairs` pairs of games between evaluator_a and evaluator_b, `games_in_flight` of them in lock step.
 
@@ -176,10 +173,6 @@ class Arena:
         self.pair_id.copy_(torch.clamp(gid, min=0) // 2)
         self.search.set_game_ids(torch.clamp(gid, min=0))
 
-    def _stream(self):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def running(self):
         """Number of slots that still hold a game."""
         return sum(1 for g in self._slot_game if g >= 0)
@@ -190,7 +183,7 @@ class Arena:
         from ._lib import check
         over, winner = self.env.terminal()
         check(self.L.hive_arena_score_launch(_p(boards), _p(over), _p(winner), _p(self.active), _p(self.a_white), self.n,
-                                             MAX_GAME_LENGTH, _p(self.result_codes), _p(self.tally), self._stream()))
+                                             MAX_GAME_LENGTH, _p(self.result_codes), _p(self.tally), stream_ptr(self.device)))
         codes = self.result_codes.cpu().numpy()
         slots = [int(s) for s in codes.nonzero()[0]]
         if not slots:
@@ -232,7 +225,7 @@ class Arena:
             action = self.search.action.fill_(-2)
         check(self.L.hive_arena_opening_launch(_p(boards), _p(count), _p(lst), _p(self.pair_id), _p(self.active), self.n,
                                                ctypes.c_uint64(self.seed & (2 ** 64 - 1)), self.opening_turns, _p(action),
-                                               self._stream()))
+                                               stream_ptr(self.device)))
         if forced is not None:
             forced = torch.as_tensor(forced, dtype=torch.int32, device=self.device)
             action = torch.where((forced >= -1) & (action != -2), forced, action)

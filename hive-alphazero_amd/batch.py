@@ -9,14 +9,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (BF16, BOARD_BYTES, CHW, F16, F32, HISTORY_BYTES, HIVE_LIST_CAP, HIVE_MASK_WORDS, HWC,
-                   check, load)
-
-_DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+from ._lib import (BOARD_BYTES, CHW, HISTORY_BYTES, HIVE_LIST_CAP, HIVE_MASK_WORDS, HWC, check, dtype_code, load,
+                   ptr as _ptr, stream_ptr)
 
 
 class BoardBatch:
@@ -34,8 +28,7 @@ class BoardBatch:
         self._sync_stream()
 
     def _sync_stream(self):
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        check(self._L.hive_batch_set_stream(self._h, ctypes.c_void_p(s)))
+        check(self._L.hive_batch_set_stream(self._h, stream_ptr(self.device)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -87,7 +80,7 @@ class BoardBatch:
         if out is None:
             out = torch.empty(shape, dtype=dtype, device=self.device)
         assert out.is_contiguous() and out.numel() == self.n * 8064 and out.dtype == dtype
-        check(self._L.hive_batch_encode(self._h, _ptr(out), _DT[dtype], HWC if layout == "hwc" else CHW))
+        check(self._L.hive_batch_encode(self._h, _ptr(out), dtype_code(dtype), HWC if layout == "hwc" else CHW))
         return out
 
     # ---- GamePlay.game_is_over
@@ -128,6 +121,6 @@ def movegen(boards, want_list=False, stream=None):
     mask = torch.empty((n, HIVE_MASK_WORDS), dtype=torch.int32, device=dev)
     count = torch.empty((n,), dtype=torch.int32, device=dev)
     lst = torch.empty((n, HIVE_LIST_CAP), dtype=torch.int16, device=dev) if want_list else None
-    s = (stream or torch.cuda.current_stream(dev)).cuda_stream
-    check(L.hive_movegen_launch(_ptr(boards), n, _ptr(mask), _ptr(count), _ptr(lst), ctypes.c_void_p(s)))
+    s = ctypes.c_void_p(stream.cuda_stream) if stream else stream_ptr(dev)
+    check(L.hive_movegen_launch(_ptr(boards), n, _ptr(mask), _ptr(count), _ptr(lst), s))
     return mask, count, lst

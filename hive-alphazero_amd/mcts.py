@@ -10,14 +10,9 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import BF16, F16, F32, HIVE_MASK_WORDS, HWC, check, load
+from ._lib import HIVE_MASK_WORDS, HWC, check, dtype_code, load, ptr as _p, stream_ptr
 from .config import MAX_GAME_LENGTH
-
-_DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+from .records import PlyLog, concat_packed, packed_games, rows_from_game, unpack_game
 
 
 PUCT, UCT = 0, 1           # HiveSearchMode (include/hive_search.h)
@@ -45,7 +40,7 @@ class TreeSearch:
             raise _lib.HiveError(-2, "no HIP device visible: hive_alphazero_amd has no CPU path")
         if plane_dtype is None:      # the evaluator's own input type (the plane values 0 / 1 / turn are exact in all three)
             plane_dtype = getattr(evaluator, "dtype", torch.bfloat16)
-            if plane_dtype not in _DT:
+            if plane_dtype not in (torch.float32, torch.float16, torch.bfloat16):
                 plane_dtype = torch.bfloat16
         self.L = L
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
@@ -130,7 +125,7 @@ class TreeSearch:
             pass
 
     def _stream(self):
-        s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        s = stream_ptr(self.device)
         check(self.L.hive_search_set_stream(self._h, s))
         return s
 
@@ -175,7 +170,7 @@ class TreeSearch:
             for sl in range(k):
                 check(L.hive_search_select(self._h, sl, _p(self.leaf_boards[sl * G:]), _p(self.leaf_hist[sl * G:])))
             n = k * G
-            check(L.hive_leaf_launch(_p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.planes), _DT[self.plane_dtype],
+            check(L.hive_leaf_launch(_p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.planes), dtype_code(self.plane_dtype),
                                      HWC, _p(self.workspace), _p(self.leaf_mask), _p(self.leaf_count),
                                      _p(self.leaf_over), _p(self.leaf_winner), s))
             if first and keep_root_planes:
@@ -312,11 +307,13 @@ class SelfPlay:
     move resampling -- is keyed on (seed, i, turn, simulation), so its record does not depend on the slot, batch
     size, process or GPU it ran on.  When the iterator is exhausted a finishing slot goes idle.
 
-    Finished games pile up in `finished_games` as (value_white, plies, game_id) until the caller takes them with
-    `drain_finished()`; more than `max_finished_kept` undrained games are dropped and counted (`dropped_games`,
-    one warning).  packed_records=True collects them as packed batches instead (records.pack_games' arrays, built with
-    array operations straight from the per-ply host copies: no per-row Python objects, sparse policies) --
-    `drain_finished_packed()`; what SelfPlayWorker's children send to the parent."""
+    The host side of the records is records.PlyLog: it keeps the per-ply host copies and cuts the games that end on a
+    ply into one packed batch (records.pack_games' arrays: no per-row Python objects, sparse policies).  This class owns
+    only the GPU side of that: the copy stream, the pinned staging buffers and their events.  `packed_records` selects the
+    container the caller drains: True keeps the batches (`drain_finished_packed()`; what SelfPlayWorker's children send
+    to the parent), False expands every game of a batch into `finished_games` as (value_white, plies, game_id)
+    (`drain_finished()`; per-row tuples with dense policies, for a few hundred games).  More than `max_finished_kept`
+    undrained games are dropped and counted (`dropped_games`, one warning)."""
 
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  keep_records=True, game_ids=None, max_finished_kept=1024, report_every=0, log=print, packed_records=False,
@@ -341,20 +338,15 @@ class SelfPlay:
         self.active = (self.game_id >= 0).to(torch.int8)
         self.search.set_game_ids(torch.clamp(self.game_id, min=0))
         # host copies of every ply still needed by a running game (features, history, policy, records, moved?)
-        self._log = []
-        self._pinned_pool = []       # page-locked staging sets waiting to be reused (play_ply / _settle)
-        self._start_ply = [0] * games   # ply counter at which the game in each slot started
-        self._unlogged = [False] * games   # opening plies of this slot's game were played outside play_ply (stagger)
-        self.finished_games = []
+        self._plylog = PlyLog(games, max_finished_kept)
+        self._pinned_pool = []       # page-locked staging sets waiting to be reused (play_ply)
+        self.finished_games = []     # finished games as tuples (packed_records=False)
         self.packed_records = bool(packed_records)
         self.finished_packed = []    # packed batches of finished games (packed_records=True)
-        self._packed_waiting = 0
-        self.max_finished_kept = max_finished_kept
-        self.dropped_games = self.unrecorded_games = 0
         self.report_every, self._log_fn, self._reported = report_every, log, 0
         # per-ply record copies leave on a side stream into pinned host buffers while the next search runs
         self._copy_stream = torch.cuda.Stream(self.device) if keep_records else None
-        self._copy_done = None       # event of the newest record copy (entries of self._log are valid once it has passed)
+        self._copy_done = None       # event of the newest record copy (the log's entries are valid once it has passed)
 
     def stagger(self, seed=0):
         """Spread the games over plies 0..53 with uniformly random legal moves so that a timed window
@@ -370,7 +362,7 @@ class SelfPlay:
             a = pick_uniform(count, lst, gen)
             go = (target > ply) & (over == 0) & (self.active != 0)
             self.env.step(torch.where(go, a, torch.full_like(a, -2)), sync=False)
-        self._unlogged = [bool(t > 0) for t in target.cpu().tolist()]
+        self._plylog.unlogged = [bool(t > 0) for t in target.cpu().tolist()]
 
     def running(self):
         """Number of slots that still hold a game."""
@@ -394,13 +386,10 @@ class SelfPlay:
             slots = idx.cpu().tolist()
             if self.keep_records:
                 self._close_games(slots, winner.cpu().tolist(), self.game_id.cpu().tolist())
-            else:
-                for s in slots:
-                    self._start_ply[s], self._unlogged[s] = self.plies, False
             fresh = [next(self._ids, -1) for _ in slots]
             for sl, f in zip(slots, fresh):
                 if f < 0:
-                    self._start_ply[sl] = 1 << 60          # idle from now on: nothing of the log belongs to it
+                    self._plylog.idle(sl)
             self.game_id[idx.long()] = torch.tensor(fresh, dtype=torch.int64, device=self.device)
             self.active = (self.game_id >= 0).to(torch.int8)
             self.search.set_game_ids(torch.clamp(self.game_id, min=0))
@@ -428,103 +417,17 @@ class SelfPlay:
             self._copy_done.synchronize()
 
     def _close_games(self, slots, winner, ids):
-        """self_play.py:165-191: value_white = +1 / -1 / 0; a draw or the length cap scores -1 for both."""
-        import warnings
+        """The games that ended leave the log as one packed batch, kept as it is or expanded game by game."""
         self._log_ready()
-        keep = []                        # (slot, first logged ply, value_white, game id)
-        for s in slots:
-            start, self._start_ply[s] = self._start_ply[s], self.plies
-            unlogged, self._unlogged[s] = self._unlogged[s], False
-            if unlogged:
-                self.unrecorded_games += 1
-                continue
-            if len(self.finished_games) + self._packed_waiting + len(keep) >= self.max_finished_kept:
-                if self.dropped_games == 0:
-                    warnings.warn(f"SelfPlay: more than {self.max_finished_kept} finished games are waiting; call "
-                                  "drain_finished() -- further games are dropped (dropped_games counts them)")
-                self.dropped_games += 1
-                continue
-            keep.append((s, start, 1 if winner[s] == 1 else (-1 if winner[s] == 2 else 0), ids[s]))
-        if self.packed_records:
-            packed = self._pack_from_log(keep) if keep else None
-            if packed is not None:
-                self.finished_packed.append(packed)
-                self._packed_waiting += len(packed["game_val"])
-            return
-        for s, start, vw, gid in keep:
-            plies = [self.ply_record(e, s) for e in self._log if e["ply"] >= start and e["moved"][s]]
-            if plies:
-                self.finished_games.append((vw, plies, gid))
+        waiting = len(self.finished_games) + sum(packed_games(b) for b in self.finished_packed)
+        packed = self._plylog.close_games(slots, winner, ids, self.plies, waiting)
+        if packed is not None and self.packed_records:
+            self.finished_packed.append(packed)
+        elif packed is not None:
+            self.finished_games += [unpack_game(packed, g) for g in range(packed_games(packed))]
 
-    @staticmethod
-    def _entry_csr(e):
-        """The visit policies of one logged ply (all game slots) as CSR, computed once per ply."""
-        if "csr" not in e:
-            from .records import _csr
-            e["csr"] = _csr(e["policy"])
-        return e["csr"]
-
-    def _settle(self, e):
-        """A logged ply whose device-to-host copy has completed leaves its page-locked staging buffers: the packed route
-        keeps the sparse policies (the dense 1584-wide rows, 6.5 MB per ply at 1024 games, are dropped) and pageable copies of
-        the small arrays; the row-wise route keeps pageable copies of everything.  The staging set goes back to the pool."""
-        import numpy as np
-        pinned = e.pop("_pinned", None)
-        if pinned is None:
-            return
-        if self.packed_records:
-            self._entry_csr(e)
-            e.pop("policy", None)
-        for k in ("feat", "policy", "boards", "hist", "moved"):
-            if k in e:
-                e[k] = np.array(e[k])
-        self._pinned_pool.append(pinned)
-
-    def _pack_from_log(self, keep):
-        """The games in `keep` as one packed batch (records.pack_games' arrays; rows grouped by game, plies ascending) --
-        the same rows ply_record would cut out one by one, gathered per logged ply with array operations."""
-        import numpy as np
-        S = np.asarray([k[0] for k in keep], dtype=np.int64)
-        start = np.asarray([k[1] for k in keep], dtype=np.int64)
-        feat, hist, meta, cnt, pidx, pval, gk, ply = [], [], [], [], [], [], [], []
-        for e in self._log:
-            k = np.flatnonzero(np.asarray(e["moved"])[S] & (e["ply"] >= start))
-            if k.size == 0:
-                continue
-            sl = S[k]
-            b = e["boards"]
-            turn = b[sl, 33].astype(np.int64)
-            persp = np.where(turn % 2 == 1, 0, 1)
-            hl = b[sl, 35].astype(np.int64)
-            hlen = np.where(persp == 0, hl & 15, hl >> 4)
-            feat.append(e["feat"][sl])
-            hist.append(e["hist"][sl, persp])
-            meta.append(np.stack([hlen, turn, persp], axis=1).astype(np.uint8))
-            ptr, idx, val = self._entry_csr(e)
-            c = ptr[sl + 1] - ptr[sl]
-            src = np.repeat(ptr[sl] - (np.cumsum(c) - c), c) + np.arange(int(c.sum()))
-            cnt.append(c)
-            pidx.append(idx[src])
-            pval.append(val[src])
-            gk.append(k)
-            ply.append(np.full(k.size, e["ply"], dtype=np.int64))
-        if not feat:
-            return None
-        gk, ply, cnt = np.concatenate(gk), np.concatenate(ply), np.concatenate(cnt)
-        order = np.lexsort((ply, gk))                           # rows by game, plies ascending
-        old_ptr = np.cumsum(cnt) - cnt
-        c = cnt[order]
-        new_ptr = np.zeros(len(c) + 1, dtype=np.int64)
-        np.cumsum(c, out=new_ptr[1:])
-        src = np.repeat(old_ptr[order] - new_ptr[:-1], c) + np.arange(int(new_ptr[-1]))
-        rows_per_game = np.bincount(gk, minlength=len(keep))
-        has = rows_per_game > 0                                 # a game without a logged row leaves no entry (as the row-wise path)
-        game_ptr = np.zeros(int(has.sum()) + 1, dtype=np.int64)
-        np.cumsum(rows_per_game[has], out=game_ptr[1:])
-        return {"feat": np.concatenate(feat)[order], "hist": np.concatenate(hist)[order], "meta": np.concatenate(meta)[order],
-                "pol_idx": np.concatenate(pidx)[src], "pol_val": np.concatenate(pval)[src], "pol_ptr": new_ptr,
-                "game_ptr": game_ptr, "game_val": np.asarray([k[2] for k in keep], dtype=np.int8)[has],
-                "game_id": np.asarray([k[3] for k in keep], dtype=np.int64)[has]}
+    dropped_games = property(lambda self: self._plylog.dropped_games)
+    unrecorded_games = property(lambda self: self._plylog.unrecorded_games)
 
     def drain_finished(self):
         """Take (and forget) every finished game collected so far: list of (value_white, plies, game_id);
@@ -535,36 +438,17 @@ class SelfPlay:
     def drain_finished_packed(self):
         """packed_records=True: take (and forget) the finished games collected so far as ONE packed batch
         (records.pack_games' arrays; records.unpack_game / PackedGames expand them), or None if there are none."""
-        from . import records
-        batches, self.finished_packed, self._packed_waiting = self.finished_packed, [], 0
-        return records.concat_packed(batches) if batches else None
+        batches, self.finished_packed = self.finished_packed, []
+        return concat_packed(batches) if batches else None
 
-    @staticmethod
-    def ply_record(entry, g):
-        """(packed features uint64[144], history words uint32[4,2,6], valid entries, turn, policy, mover) of game
-        slot g at one logged ply."""
-        turn = int(entry["boards"][g, 33])
-        persp = 0 if turn % 2 == 1 else 1
-        hl = int(entry["boards"][g, 35])
-        hlen = (hl & 15) if persp == 0 else (hl >> 4)
-        if "policy" in entry:
-            policy = entry["policy"][g].copy()
-        else:                                    # a settled ply of the packed route keeps the sparse form only
-            import numpy as np
-            ptr, idx, val = entry["csr"]
-            policy = np.zeros(1584, dtype=np.float32)
-            policy[idx[ptr[g]:ptr[g + 1]]] = val[ptr[g]:ptr[g + 1]]
-        return (entry["feat"][g].copy(), entry["hist"][g, persp].copy(), hlen, turn, policy, persp)
+    ply_record = staticmethod(PlyLog.ply_record)    # (entry of the log, slot) -> one ply tuple
 
     def last_ply_record(self, g):
         self._log_ready()
-        return self.ply_record(self._log[-1], g) if self._log and self._log[-1]["moved"][g] else None
+        log = self._plylog.entries
+        return self.ply_record(log[-1], g) if log and log[-1]["moved"][g] else None
 
-    @staticmethod
-    def game_rows(entry):
-        """One finished game as the reference's JSON rows [state, policy, value, [game_len, counter]]."""
-        from . import records
-        return records.rows_from_game(entry)
+    game_rows = staticmethod(rows_from_game)        # one finished game -> the reference's JSON rows
 
     def finished_game_rows(self, k):
         """The k-th waiting finished game as the reference's rows."""
@@ -596,7 +480,7 @@ class SelfPlay:
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream(self.device))
             prev_copy = self._copy_done
-            # page-locked staging buffers are recycled: a ply's arrays move to pageable memory one ply later (_settle), so
+            # page-locked staging buffers are recycled: a ply's arrays move to pageable memory one ply later (settle), so
             # two or three sets exist per engine instead of one per ply of the longest running game (8-32 MB each)
             host = self._pinned_pool.pop() if self._pinned_pool else \
                 {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True) for k, v in src.items()}
@@ -607,23 +491,16 @@ class SelfPlay:
                     v.record_stream(self._copy_stream)
                 self._copy_done = torch.cuda.Event()
                 self._copy_done.record(self._copy_stream)
-            self._log.append({
-                "ply": self.plies,
-                "feat": host["feat"].numpy().view("uint64"),
-                "policy": host["policy"].numpy(),
-                "boards": host["boards"].numpy(),
-                "hist": host["hist"].numpy().view("uint32").reshape(self.games, 2, 4, 2, 6),
-                "moved": host["moved"].numpy(),
-                "_pinned": host,                 # keeps the pinned tensors (the arrays above are views) alive
-            })
-            oldest = min(self._start_ply)
-            while self._log and self._log[0]["ply"] < oldest:
-                self._log.pop(0)
-            if len(self._log) >= 2 and prev_copy is not None:
+            # (the arrays are views of the pinned tensors: `host` travels along as the entry's keepalive)
+            log = self._plylog
+            log.append(self.plies, keepalive=host, **{k: v.numpy() for k, v in host.items()})
+            if len(log.entries) >= 2 and prev_copy is not None:
                 # the previous ply's copy was issued a whole search ago: its sparse policies are built now, while the GPU
                 # runs this ply's search (the host has nothing else to do), not when a thousand games end at once
                 prev_copy.synchronize()
-                self._settle(self._log[-2])
+                freed = log.settle(log.entries[-2])
+                if freed is not None:
+                    self._pinned_pool.append(freed)
         if forced is not None:
             forced = torch.as_tensor(forced, dtype=torch.int32, device=self.device)
             action = torch.where((forced >= -1) & (action != -2), forced, action)

@@ -2,7 +2,7 @@
 
 woker/self_play.py:100-112,178-193 writes `play_<ts>.json` = list of
 `[state[12][12][56], policy[1584], value, [game_len, counter]]`; woker/optimize.py:42-65 loads it
-and applies `value * 0.99 ** (game_len - step)`.  The GPU engine keeps, per ply, the packed 56-bit
+and discounts the value by the moves still to come (load_data).  The GPU engine keeps, per ply, the packed 56-bit
 features of every game (1,152 B instead of the 64 KB float64 planes), the visit policy and the mover;
 this module expands finished games into those entries.
 
@@ -10,6 +10,11 @@ One MI355X plays ~4,000 games/min = ~3,400 rows/s; as JSON that is ~13 GB/min of
 Python can format.  `save_games / load_games` therefore keep finished games as they leave the GPU -- packed features,
 history bitboards, sparse visit policy: ~1.5 KB per row in an .npz -- and `dataset_from_games` / `rows_from_game` expand
 them into exactly what the JSON route yields (same planes, same discounted values) when the trainer asks.
+
+There is one record route.  `PlyLog` (plain numpy, no GPU) keeps the engine's per-ply host copies and cuts the games that
+end into ONE form, the packed batch (`PACKED_KEYS`); a (value_white, plies, game id) tuple is a view of it (`unpack_game`),
+the training value of a row is `packed_values`, and the dataset_* functions are built on those two.  `game_entries` and
+`load_data` restate the reference's own two functions and stay independent of all that: the tests compare against them.
 """
 import json
 import os
@@ -165,14 +170,19 @@ def concat_packed(batches):
 def unpack_game(packed, g):
     """Game g of a packed batch as SelfPlay collects it: (value_white, plies, game id), plies =
     (features uint64[144], history words uint32[4,2,6], valid entries, turn, dense policy float32[1584], mover)."""
-    pol_idx, pol_val, pol_ptr, meta = packed["pol_idx"], packed["pol_val"], packed["pol_ptr"], packed["meta"]
-    plies = []
-    for r in range(int(packed["game_ptr"][g]), int(packed["game_ptr"][g + 1])):
-        policy = np.zeros(1584, dtype=np.float32)
-        lo, hi = int(pol_ptr[r]), int(pol_ptr[r + 1])
-        policy[pol_idx[lo:hi]] = pol_val[lo:hi]
-        plies.append((packed["feat"][r], packed["hist"][r], int(meta[r, 0]), int(meta[r, 1]), policy, int(meta[r, 2])))
+    meta, csr = packed["meta"], (packed["pol_ptr"], packed["pol_idx"], packed["pol_val"])
+    plies = [(packed["feat"][r], packed["hist"][r], int(meta[r, 0]), int(meta[r, 1]), _dense_row(csr, r), int(meta[r, 2]))
+             for r in range(int(packed["game_ptr"][g]), int(packed["game_ptr"][g + 1]))]
     return (int(packed["game_val"][g]), plies, int(packed["game_id"][g]))
+
+
+def _dense_row(csr, r):
+    """float32[1584]: row r of the (ptr, column, value) form _csr builds."""
+    ptr, idx, val = csr
+    policy = np.zeros(1584, dtype=np.float32)
+    lo, hi = int(ptr[r]), int(ptr[r + 1])
+    policy[idx[lo:hi]] = val[lo:hi]
+    return policy
 
 
 class PackedGames:
@@ -289,70 +299,11 @@ def load_games(path):
     return [unpack_game(packed, g) for g in range(packed_games(packed))]
 
 
-def dataset_from_games(games):
-    """What woker/optimize.py:42-65 builds from the JSON rows, straight from compact games: (states float32 [N,12,12,56],
-    policies float32 [N,1584], values float32 [N]) with value * 0.99 ** (game_len - step) applied."""
-    states, policies, values = [], [], []
-    for entry in games:
-        vw, plies = entry[0], entry[1]
-        total = [sum(1 for p in plies if p[5] == s) for s in (0, 1)]
-        seen = [0, 0]
-        for words, hw, hlen, turn, policy, mover in plies:
-            seen[mover] += 1
-            value = -1.0 if vw == 0 else float(vw if mover == 0 else -vw)
-            if seen[mover] != total[mover]:
-                value = value * DISCOUNTED_REWARD ** (total[mover] - seen[mover])
-            states.append(unpack_features(words, turn, history_planes(hw, hlen)).astype(np.float32))
-            policies.append(np.asarray(policy, dtype=np.float32))
-            values.append(value)
-    return np.stack(states), np.stack(policies), np.asarray(values, dtype=np.float32)
-
-
-def dataset_tensors_gpu(games, device=None, dtype=None, layout="chw"):
-    """dataset_from_games on the GPU: the packed features, history bitboards and turn bytes of every row are uploaded
-    (1.5 KB per row) and widened to planes by the env's own plane writer (hive_expand_launch) -- what a trainer that
-    keeps up with the self-play GPUs uses.  -> (states [N,56,12,12] ("chw", what ChessNet takes) or [N,12,12,56],
-    policies float32 [N,1584], values float32 [N]) on `device`, values discounted like woker/optimize.py:42-65."""
-    import ctypes
-    import torch
-    from . import _lib
-    L = _lib.load()
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    dtype = dtype or torch.float32
-    rows = [(g[0], p, sum(1 for q in g[1] if q[5] == p[5]), sum(1 for q in g[1][:k + 1] if q[5] == p[5]))
-            for g in games for k, p in enumerate(g[1])]
-    n = len(rows)
-    if n == 0:                      # nothing to widen (hive_expand_launch refuses n <= 0)
-        shape = (0, 56, 12, 12) if layout == "chw" else (0, 12, 12, 56)
-        return (torch.zeros(shape, dtype=dtype, device=dev), torch.zeros((0, 1584), dtype=torch.float32, device=dev),
-                torch.zeros((0,), dtype=torch.float32, device=dev))
-    boards = np.zeros((n, 64), dtype=np.uint8)
-    hist = np.zeros((n, 2, 4, 2, 6), dtype=np.uint32)
-    feat = np.zeros((n, 144), dtype=np.uint64)
-    policies = np.zeros((n, 1584), dtype=np.float32)
-    values = np.zeros(n, dtype=np.float32)
-    for i, (vw, (words, hw, hlen, turn, policy, mover), total, seen) in enumerate(rows):
-        feat[i] = np.asarray(words, dtype=np.uint64).reshape(144)
-        hist[i, mover] = np.asarray(hw, dtype=np.uint32).reshape(4, 2, 6)
-        boards[i, 33] = turn
-        boards[i, 35] = (int(hlen) & 15) if mover == 0 else (int(hlen) << 4)
-        policies[i] = policy
-        value = -1.0 if vw == 0 else float(vw if mover == 0 else -vw)
-        values[i] = value if seen == total else value * DISCOUNTED_REWARD ** (total - seen)
-    shape = (n, 56, 12, 12) if layout == "chw" else (n, 12, 12, 56)
-    planes = torch.empty(shape, dtype=dtype, device=dev)
-    tb, th = torch.from_numpy(boards).to(dev), torch.from_numpy(hist.view(np.uint8).reshape(n, 384)).to(dev)
-    tf = torch.from_numpy(feat.view(np.int64)).to(dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    dt = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}[dtype]
-    _lib.check(L.hive_expand_launch(p(tb), p(th), p(tf), n, p(planes), dt, _lib.CHW if layout == "chw" else _lib.HWC,
-                                    ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    return planes, torch.from_numpy(policies).to(dev), torch.from_numpy(values).to(dev)
-
-
 def packed_values(packed):
     """float32[R]: the training value of every row of a packed batch -- value_white from the mover's side (draw / length cap
-    = -1 for both, self_play.py:178-191), discounted by 0.99 ** (moves of that side still to come), optimize.py:42-65."""
+    = -1 for both, self_play.py:178-191), discounted by DISCOUNTED_REWARD ** (moves of that side still to come),
+    optimize.py:42-65.  THE implementation of that rule for everything built from packed batches (the dataset_* functions
+    below; replay.discount_table tabulates it for the device); load_data above is the reference's own statement of it."""
     gp = packed["game_ptr"]
     n = int(gp[-1]) if len(gp) else 0
     gi = np.repeat(np.arange(len(gp) - 1), np.diff(gp))
@@ -369,37 +320,201 @@ def packed_values(packed):
     return np.where(left > 0, value * table[left], value).astype(np.float32)
 
 
-def dataset_tensors_gpu_packed(packed, device=None, dtype=None, layout="chw"):
-    """dataset_tensors_gpu for a packed batch (records.load_packed / SelfPlay.drain_finished_packed) without a Python
-    object per row: the packed features, history words and turn bytes go up as they are (1.5 KB per row), the env's plane
-    writer widens them (hive_expand_launch), the sparse policies are scattered into the dense matrix on the GPU."""
-    import ctypes
-    import torch
-    from . import _lib
-    L = _lib.load()
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    dtype = dtype or torch.float32
-    n = len(packed["meta"])
-    shape = (n, 56, 12, 12) if layout == "chw" else (n, 12, 12, 56)
-    if n == 0:
-        return (torch.zeros(shape, dtype=dtype, device=dev), torch.zeros((0, 1584), dtype=torch.float32, device=dev),
-                torch.zeros((0,), dtype=torch.float32, device=dev))
-    meta = packed["meta"].astype(np.int64)
+def dataset_from_packed(packed):
+    """What woker/optimize.py:42-65 builds from the JSON rows, straight from a packed batch: (states float32 [N,12,12,56],
+    policies float32 [N,1584], values float32 [N] = packed_values)."""
+    meta, csr = packed["meta"], (packed["pol_ptr"], packed["pol_idx"], packed["pol_val"])
+    states = [unpack_features(packed["feat"][r], int(meta[r, 1]), history_planes(packed["hist"][r], int(meta[r, 0]))).astype(np.float32)
+              for r in range(len(meta))]
+    return np.stack(states), np.stack([_dense_row(csr, r) for r in range(len(meta))]), packed_values(packed)
+
+
+def dataset_from_games(games):
+    """dataset_from_packed for finished games (value_white, plies[, game id]) as SelfPlay / load_games hand them out."""
+    return dataset_from_packed(pack_games(games))
+
+
+def board_records(meta, hist):
+    """The rows of a packed batch as the env's records (include/hive_abi.h): boards u8[n,64] with the turn in byte 33 and
+    the number of valid history entries in the mover's nibble of byte 35, hist u32[n,2,4,2,6] with the history words in the
+    mover's half -- all that hive_expand_launch reads besides the packed features."""
+    meta = np.asarray(meta).astype(np.int64)
+    n = len(meta)
     hlen, turn, mover = meta[:, 0], meta[:, 1], meta[:, 2]
     boards = np.zeros((n, 64), dtype=np.uint8)
     boards[:, 33] = turn
     boards[:, 35] = np.where(mover == 0, hlen & 15, (hlen << 4) & 255)
-    hist = np.zeros((n, 2, 4, 2, 6), dtype=np.uint32)
-    hist[np.arange(n), mover] = packed["hist"]
-    planes = torch.empty(shape, dtype=dtype, device=dev)
-    tb, th = torch.from_numpy(boards).to(dev), torch.from_numpy(hist.view(np.uint8).reshape(n, 384)).to(dev)
-    tf = torch.from_numpy(np.ascontiguousarray(packed["feat"]).view(np.int64)).to(dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    dt = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}[dtype]
-    _lib.check(L.hive_expand_launch(p(tb), p(th), p(tf), n, p(planes), dt, _lib.CHW if layout == "chw" else _lib.HWC,
-                                    ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    out = np.zeros((n, 2, 4, 2, 6), dtype=np.uint32)
+    out[np.arange(n), mover] = hist
+    return boards, out
+
+
+def expand_planes(boards, hist, feat, device, dtype, layout):
+    """Host records (board_records' arrays + feat u64[n,144], n >= 1) -> the planes on `device`, widened by the env's own
+    plane writer (hive_expand_launch): [n,56,12,12] for layout "chw", else [n,12,12,56]."""
+    import torch
+    from . import _lib
+    n = len(boards)
+    planes = torch.empty((n, 56, 12, 12) if layout == "chw" else (n, 12, 12, 56), dtype=dtype, device=device)
+    tb = torch.from_numpy(boards).to(device)
+    th = torch.from_numpy(hist.view(np.uint8).reshape(n, 384)).to(device)
+    tf = torch.from_numpy(np.ascontiguousarray(feat).view(np.int64)).to(device)
+    _lib.check(_lib.load().hive_expand_launch(_lib.ptr(tb), _lib.ptr(th), _lib.ptr(tf), n, _lib.ptr(planes), _lib.dtype_code(dtype),
+                                              _lib.CHW if layout == "chw" else _lib.HWC, _lib.stream_ptr(device)))
+    return planes
+
+
+def dataset_tensors_gpu_packed(packed, device=None, dtype=None, layout="chw"):
+    """dataset_from_packed on the GPU, without a Python object per row (records.load_packed /
+    SelfPlay.drain_finished_packed): the packed features, history words and turn bytes go up as they are (1.5 KB per row),
+    the env's plane writer widens them, the sparse policies are scattered into the dense matrix on the GPU -- what a trainer
+    that keeps up with the self-play GPUs uses.  -> (states [N,56,12,12] ("chw", what ChessNet takes) or [N,12,12,56],
+    policies float32 [N,1584], values float32 [N] = packed_values) on `device`."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    dtype = dtype or torch.float32
+    n = len(packed["meta"])
+    if n == 0:                      # nothing to widen (hive_expand_launch refuses n <= 0)
+        shape = (0, 56, 12, 12) if layout == "chw" else (0, 12, 12, 56)
+        return (torch.zeros(shape, dtype=dtype, device=dev), torch.zeros((0, 1584), dtype=torch.float32, device=dev),
+                torch.zeros((0,), dtype=torch.float32, device=dev))
+    planes = expand_planes(*board_records(packed["meta"], packed["hist"]), packed["feat"], dev, dtype, layout)
     rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(packed["pol_ptr"]))
     flat = torch.from_numpy(rows * 1584 + packed["pol_idx"].astype(np.int64)).to(dev)
     policies = torch.zeros((n * 1584,), dtype=torch.float32, device=dev)
     policies[flat] = torch.from_numpy(np.ascontiguousarray(packed["pol_val"])).to(dev)
     return planes, policies.view(n, 1584), torch.from_numpy(packed_values(packed)).to(dev)
+
+
+def dataset_tensors_gpu(games, device=None, dtype=None, layout="chw"):
+    """dataset_tensors_gpu_packed for finished games (value_white, plies[, game id])."""
+    return dataset_tensors_gpu_packed(pack_games(games), device, dtype, layout)
+
+
+# ------------------------------------------------------------------ the per-ply host log
+class PlyLog:
+    """The host side of SelfPlay's records: whole-batch numpy copies of every ply a running game may still need, and the one
+    cutter that turns the games ending on a ply into a packed batch (pack_games' arrays, gathered per logged ply with array
+    operations: no per-row Python objects).  Plain numpy: the GPU side (copy stream, pinned staging buffers) stays with
+    the caller, which hands the staging set in as an opaque `keepalive` and gets it back from `settle`.
+
+    More than `max_finished_kept` games waiting at the caller are dropped and counted (`dropped_games`, one warning); a game
+    whose opening was played outside the log (`unlogged[slot]`) is counted in `unrecorded_games` and leaves nothing."""
+
+    IDLE = 1 << 60                   # start ply of a slot that holds no game: nothing of the log belongs to it
+
+    def __init__(self, slots, max_finished_kept=1024):
+        self.entries = []                    # one dict per logged ply, oldest first
+        self.start_ply = [0] * slots         # ply counter at which the game in each slot started
+        self.unlogged = [False] * slots      # opening plies of this slot's game were not logged
+        self.max_finished_kept = max_finished_kept
+        self.dropped_games = self.unrecorded_games = 0
+
+    def append(self, ply, feat, policy, boards, hist, moved, keepalive=None):
+        """One ply of every slot: feat u64[G,144] (or its int64 bits), dense policy f32[G,1584], board records u8[G,64],
+        history u32[G,2,4,2,6] (or its 384 bytes per slot), moved bool[G].  The arrays may be views into staging memory that
+        `keepalive` owns and that is still being filled: nothing is read before settle / close_games / ply_record.
+        Entries older than the oldest running game are forgotten."""
+        self.entries.append({"ply": ply, "feat": np.asarray(feat).view(np.uint64), "policy": np.asarray(policy),
+                             "boards": np.asarray(boards), "hist": np.asarray(hist).view(np.uint32).reshape(-1, 2, 4, 2, 6),
+                             "moved": np.asarray(moved), "keepalive": keepalive})
+        oldest = min(self.start_ply)
+        while self.entries and self.entries[0]["ply"] < oldest:
+            self.entries.pop(0)
+
+    @staticmethod
+    def _entry_csr(e):
+        """The visit policies of one logged ply (all slots) as CSR, computed once per ply."""
+        if "csr" not in e:
+            e["csr"] = _csr(e["policy"])
+        return e["csr"]
+
+    def settle(self, e):
+        """A logged ply whose arrays are complete leaves its staging memory: the sparse policies are kept (the dense
+        1584-wide rows, 6.5 MB per ply at 1024 games, are dropped) with copies of the small arrays.  -> the entry's
+        keepalive, free for reuse (None if it had none or was settled before)."""
+        if "policy" not in e:
+            return None
+        self._entry_csr(e)
+        del e["policy"]
+        for k in ("feat", "boards", "hist", "moved"):
+            e[k] = np.array(e[k])
+        return e.pop("keepalive", None)
+
+    @classmethod
+    def ply_record(cls, entry, g):
+        """(packed features uint64[144], history words uint32[4,2,6], valid entries, turn, policy, mover) of slot g at one
+        logged ply."""
+        turn = int(entry["boards"][g, 33])
+        persp = 0 if turn % 2 == 1 else 1
+        hl = int(entry["boards"][g, 35])
+        hlen = (hl & 15) if persp == 0 else (hl >> 4)
+        return (entry["feat"][g].copy(), entry["hist"][g, persp].copy(), hlen, turn, _dense_row(cls._entry_csr(entry), g), persp)
+
+    def idle(self, slot):
+        """The slot holds no game from now on."""
+        self.start_ply[slot] = self.IDLE
+
+    def close_games(self, slots, winner, ids, ply_now, waiting=0):
+        """The games in `slots` have ended (self_play.py:165-191: value_white = +1 / -1 / 0 from winner[slot] = 1 / 2 / other)
+        and their slots start over at `ply_now`.  -> their rows as one packed batch (games by ascending position in `slots`,
+        rows by ply; a game without a logged row leaves no entry), or None.  `waiting` = games the caller still holds."""
+        import warnings
+        keep = []                        # (slot, first logged ply, value_white, game id)
+        for s in slots:
+            start, self.start_ply[s] = self.start_ply[s], ply_now
+            unlogged, self.unlogged[s] = self.unlogged[s], False
+            if unlogged:
+                self.unrecorded_games += 1
+                continue
+            if waiting + len(keep) >= self.max_finished_kept:
+                if self.dropped_games == 0:
+                    warnings.warn(f"SelfPlay: more than {self.max_finished_kept} finished games are waiting; call "
+                                  "drain_finished() -- further games are dropped (dropped_games counts them)")
+                self.dropped_games += 1
+                continue
+            keep.append((s, start, 1 if winner[s] == 1 else (-1 if winner[s] == 2 else 0), ids[s]))
+        return self._pack(keep) if keep else None
+
+    def _pack(self, keep):
+        S = np.asarray([k[0] for k in keep], dtype=np.int64)
+        start = np.asarray([k[1] for k in keep], dtype=np.int64)
+        feat, hist, meta, cnt, pidx, pval, gk, ply = [], [], [], [], [], [], [], []
+        for e in self.entries:
+            k = np.flatnonzero(np.asarray(e["moved"])[S] & (e["ply"] >= start))
+            if k.size == 0:
+                continue
+            sl = S[k]
+            b = e["boards"]
+            turn = b[sl, 33].astype(np.int64)
+            persp = np.where(turn % 2 == 1, 0, 1)
+            hl = b[sl, 35].astype(np.int64)
+            hlen = np.where(persp == 0, hl & 15, hl >> 4)
+            feat.append(e["feat"][sl])
+            hist.append(e["hist"][sl, persp])
+            meta.append(np.stack([hlen, turn, persp], axis=1).astype(np.uint8))
+            ptr, idx, val = self._entry_csr(e)
+            c = ptr[sl + 1] - ptr[sl]
+            src = np.repeat(ptr[sl] - (np.cumsum(c) - c), c) + np.arange(int(c.sum()))
+            cnt.append(c)
+            pidx.append(idx[src])
+            pval.append(val[src])
+            gk.append(k)
+            ply.append(np.full(k.size, e["ply"], dtype=np.int64))
+        if not feat:
+            return None
+        gk, ply, cnt = np.concatenate(gk), np.concatenate(ply), np.concatenate(cnt)
+        order = np.lexsort((ply, gk))                           # rows by game, plies ascending
+        old_ptr = np.cumsum(cnt) - cnt
+        c = cnt[order]
+        new_ptr = np.zeros(len(c) + 1, dtype=np.int64)
+        np.cumsum(c, out=new_ptr[1:])
+        src = np.repeat(old_ptr[order] - new_ptr[:-1], c) + np.arange(int(new_ptr[-1]))
+        rows_per_game = np.bincount(gk, minlength=len(keep))
+        has = rows_per_game > 0                                 # a game without a logged row leaves no entry
+        game_ptr = np.zeros(int(has.sum()) + 1, dtype=np.int64)
+        np.cumsum(rows_per_game[has], out=game_ptr[1:])
+        return {"feat": np.concatenate(feat)[order], "hist": np.concatenate(hist)[order], "meta": np.concatenate(meta)[order],
+                "pol_idx": np.concatenate(pidx)[src], "pol_val": np.concatenate(pval)[src], "pol_ptr": new_ptr,
+                "game_ptr": game_ptr, "game_val": np.asarray([k[2] for k in keep], dtype=np.int8)[has],
+                "game_id": np.asarray([k[3] for k in keep], dtype=np.int64)[has]}

@@ -28,8 +28,9 @@ _M64 = (1 << 64) - 1
 
 
 def discount_table():
-    """float32[256]: DISCOUNTED_REWARD ** k computed in float64 and rounded once -- a value is +-1 times an entry of it,
-    so the device's values are records.packed_values' bit for bit."""
+    """float32[256]: the discount of records.packed_values (the one statement of the training-value rule) tabulated for the
+    device: DISCOUNTED_REWARD ** k computed in float64 and rounded once -- a value is +-1 times an entry of it, so the
+    device's values are packed_values' bit for bit."""
     return np.asarray([DISCOUNTED_REWARD ** k for k in range(256)], dtype=np.float64).astype(np.float32)
 
 
@@ -142,8 +143,7 @@ class ReplayBuffer:
         return self._h
 
     def _stream(self):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_ptr(self.device)
 
     def _up(self, a, view=None):
         import torch
@@ -183,7 +183,6 @@ class ReplayBuffer:
             self.games_seen += games
             return 0
         L, h = _lib.load(), self._handle()
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
         pol_ptr = np.ascontiguousarray(packed["pol_ptr"], dtype=np.int64)
         with torch.cuda.device(self.device):
             t = [self._up(packed["feat"], np.int64), self._up(packed["hist"], np.int32), self._up(packed["meta"]),
@@ -191,7 +190,7 @@ class ReplayBuffer:
                  self._up(np.asarray(packed["game_ptr"], dtype=np.int64)), self._up(packed["game_val"])]
             if t[2].dtype != torch.uint8 or t[3].dtype != torch.int16 or t[4].dtype != torch.float32 or t[7].dtype != torch.int8:
                 raise ValueError("packed batch: meta u8, pol_idx i16, pol_val f32, game_val i8 expected")
-            _lib.check(L.hive_replay_append(h, *[p(x) for x in t], ctypes.c_void_p(pol_ptr.ctypes.data), rows, games, self._stream()))
+            _lib.check(L.hive_replay_append(h, *[_lib.ptr(x) for x in t], ctypes.c_void_p(pol_ptr.ctypes.data), rows, games, self._stream()))
         self.rows_seen += rows
         self.games_seen += games
         return rows
@@ -205,7 +204,7 @@ class ReplayBuffer:
         dtype = dtype or torch.float32
         if layout not in LAYOUTS:
             raise ValueError(f"layout must be one of {LAYOUTS}")
-        dt = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}[dtype]
+        dt = _lib.dtype_code(dtype)
         dev = self.device
         shape = (n, 56, 12, 12) if layout == "chw" else (n, 12, 12, 56)
         if out is None:
@@ -223,7 +222,7 @@ class ReplayBuffer:
         if n:
             if len(self) == 0:
                 raise RuntimeError("the replay window is empty")
-            p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+            p = _lib.ptr
             with torch.cuda.device(dev):
                 _lib.check(_lib.load().hive_replay_sample(self._handle(), p(idx), int(seed) & _M64, int(step) & _M64,
                                                           int(stream_id) & _M64, n, dt, _lib.CHW if layout == "chw" else _lib.HWC,
@@ -267,7 +266,7 @@ class ReplayBuffer:
         feat, hist, meta = z((n, 144), torch.int64), z((n, 48), torch.int32), z((n, 4), torch.uint8)
         cnt, pidx, pval, val = z((n,), torch.int32), z((n, POLICY_CAP), torch.int16), z((n, POLICY_CAP), torch.float32), z((n,), torch.float32)
         if n:
-            p = lambda t: ctypes.c_void_p(t.data_ptr())
+            p = _lib.ptr
             with torch.cuda.device(self.device):
                 _lib.check(_lib.load().hive_replay_export(self._h, p(feat), p(hist), p(meta), p(cnt), p(pidx), p(pval), p(val),
                                                           self._stream()))
@@ -287,13 +286,12 @@ class ReplayBuffer:
         if n:
             meta = np.zeros((n, 4), dtype=np.uint8)
             meta[:, :3] = state["meta"]
-            p = lambda t: ctypes.c_void_p(t.data_ptr())
             with torch.cuda.device(self.device):
                 t = [self._up(np.asarray(state["feat"], dtype=np.uint64).reshape(n, 144), np.int64),
                      self._up(np.asarray(state["hist"], dtype=np.uint32).reshape(n, 48), np.int32), self._up(meta), self._up(cnt),
                      self._up(np.asarray(state["pol_idx"], dtype=np.int16).reshape(n, POLICY_CAP)),
                      self._up(np.asarray(state["pol_val"], dtype=np.float32).reshape(n, POLICY_CAP)),
                      self._up(np.asarray(state["values"], dtype=np.float32))]
-                _lib.check(_lib.load().hive_replay_import(self._handle(), *[p(x) for x in t], n, self._stream()))
+                _lib.check(_lib.load().hive_replay_import(self._handle(), *[_lib.ptr(x) for x in t], n, self._stream()))
         self.rows_seen = int(state["rows_seen"])
         self.games_seen = int(state["games_seen"])

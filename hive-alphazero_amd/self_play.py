@@ -90,7 +90,7 @@ def send_packed(out, rank, packed, spool):
 def _game_worker(rank, world, cfg, out):
     """One GPU's producer (child process; _child_main has set HIP_VISIBLE_DEVICES = this rank's GPU)."""
     import torch
-    from . import mcts
+    from . import mcts, records
     from .alpha_net import ChessNet, InferenceNet
     from .dist import game_id_stream
     try:
@@ -115,22 +115,22 @@ def _game_worker(rank, world, cfg, out):
         # finished_games at once, so the keep limit must cover the whole batch (this loop drains after every ply)
         compact = cfg["row_format"] == "compact"
         sp = mcts.SelfPlay(cfg["games_per_gpu"], cfg["sims"], evaluator, device=0, slots=cfg["slots"], seed=cfg["seed"],
-                           game_ids=ids, max_finished_kept=max(1024, 2 * cfg["games_per_gpu"]), packed_records=compact)
+                           game_ids=ids, max_finished_kept=max(1024, 2 * cfg["games_per_gpu"]), packed_records=True)
         out.put(("ready", rank, time.time(), 0, dict(evaluator.precision_report)))
         spool = spool_dir() if cfg.get("spool", True) else None
         while True:
             sp.play_ply()
-            if compact:
-                # the games as they left the GPU (packed features, sparse policies), every game that ended on this ply in
-                # ONE message of arrays: a thousand lock-step games ending together are 55 k rows -- 430 MB to pickle as
-                # per-row tuples with dense policies, 80 MB like this
-                packed = sp.drain_finished_packed()
-                if packed is not None:
-                    send_packed(out, rank, packed, spool)
-            else:
-                for entry in sp.drain_finished():
+            # the games as they left the GPU (packed features, sparse policies), every game that ended on this ply in ONE
+            # batch of arrays: a thousand lock-step games ending together are 55 k rows -- 430 MB to pickle as per-row
+            # tuples with dense policies, 80 MB like this
+            packed = sp.drain_finished_packed()
+            if packed is not None and compact:
+                send_packed(out, rank, packed, spool)
+            elif packed is not None:
+                for g in range(records.packed_games(packed)):
                     # the reference's rows (lists of 8,064 numbers per row: fine for a few hundred games)
-                    out.put(("game", rank, entry[2], entry[0], mcts.SelfPlay.game_rows(entry)))
+                    entry = records.unpack_game(packed, g)
+                    out.put(("game", rank, entry[2], entry[0], records.rows_from_game(entry)))
             if sp.running() == 0:
                 break
         illegal, leaves = sp.env.illegal_count(), sp.leaf_histogram()

@@ -413,6 +413,11 @@ def test_packed_game_batches_round_trip_slice_and_concat(tmp_path):
     assert [k for k, _ in view.items()] == [0, 3, 7, 11]
     # the trainer's values (optimize.py:42-65 discount) straight from the packed arrays == the row-wise rule
     assert np.array_equal(records.packed_values(packed), records.dataset_from_games(games)[2])
+    # ... == the reference's own rule: its rows (game_entries) written to a play_<ts>.json and loaded back (load_data)
+    rows = [r for vw, plies, _ in games
+            for r in records.game_entries([(np.zeros((1, 1, 1)), p[4], "W" if p[5] == 0 else "B") for p in plies], vw)]
+    loaded = records.load_data(records.flush_buffer(rows, str(tmp_path / "json")))
+    assert np.array_equal(records.packed_values(packed), np.asarray([r[2] for r in loaded], dtype=np.float32))
 
 
 def test_selfplay_worker_takes_packed_batches_from_two_ranks(tmp_path, no_device_mask):
