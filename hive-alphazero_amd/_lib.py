@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "hive_search_node_counts", "hive_search_set_transpositions", "hive_search_transposition_hits",
     "hive_search_set_game_ids", "hive_search_root_stats", "hive_search_leaf_histogram", "hive_search_sample_noise",
     "hive_search_leaf_need",
+    "hive_search_advance_roots", "hive_search_set_carry_room", "hive_search_carry_stats", "hive_search_export_tree",
     "hive_arena_split_launch", "hive_arena_join_launch", "hive_arena_opening_launch", "hive_arena_score_launch",
     # include/hive_nn.h
     "hive_nn_conv3x3", "hive_nn_resblock", "hive_nn_conv3x3_dt", "hive_nn_resblock_dt", "hive_nn_tower",
@@ -133,6 +134,10 @@ def load():
     L.hive_nn_conv3x3_sel.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     L.hive_nn_resblock_sel.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
     L.hive_search_leaf_need.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.hive_search_advance_roots.argtypes = [vp, vp, vp, vp, vp]
+    L.hive_search_set_carry_room.argtypes = [vp, i32]
+    L.hive_search_carry_stats.argtypes = [vp, vp, vp, vp]
+    L.hive_search_export_tree.argtypes = [vp, i32] + [vp] * 12
     L.hive_arena_split_launch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.hive_arena_join_launch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.hive_arena_opening_launch.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_uint64, i32, vp, vp]

@@ -44,6 +44,20 @@ struct SearchDev {
     int TT, merge;                                 // table size (power of two), merging on/off
     long long *game_id;                            // [G] global game index: the only per-game key of the noise streams
     int32_t *kind_hist;                            // [G][8] leaves by LeafKind since create (statistics)
+    int32_t *carry_kept, *carry_visits, *carry_refused;   // [G] hive_search_carry_stats
+    int sims_room;                                 // nodes a carried tree must leave free (hive_search_set_carry_room)
+};
+
+// the node arrays of one pool: hive_search_advance_roots moves the kept subtrees from the handle's pool into a second one
+struct NodePool {
+    HiveBoard *node_board;
+    HiveHistory *node_hist;
+    int32_t *node_nedge, *node_sum_n;
+    int8_t *node_term;
+    float *node_tv;
+    int16_t *e_act;
+    float *e_p, *e_w;
+    int32_t *e_n, *e_child;
 };
 
 // ------------------------------------------------------------------ small device helpers
@@ -599,6 +613,144 @@ search_noise_kernel(unsigned long long seed, long long first_game, unsigned turn
     }
 }
 
+// lanes of one wave see each other's LDS / global writes made before this point
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// hive_search_advance_roots: the subtree under the played root edge becomes the tree of the next search.  One wave per
+// game; LDS per wave: map[MN] (old node -> new index, -1 = not reached) and queue[MN] (breadth-first order = the new
+// numbering).  The kept nodes are written into the second pool D; the host swaps the pools after the launch.  Every
+// loop is bounded by MN (a node enters the queue once), 64 (lanes of a ballot) or TT.
+__global__ void __launch_bounds__(256)
+search_advance_kernel(SearchDev S, NodePool D, const int32_t *__restrict__ played, const HiveBoard *__restrict__ boards,
+                      const HiveHistory *__restrict__ hist, const int8_t *__restrict__ active)
+{
+    extern __shared__ int32_t advance_lds[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int g = blockIdx.x * (int)(blockDim.x >> 6) + wv;
+    if (g >= S.G) return;
+    int32_t *map = advance_lds + (long long)wv * 2 * S.MN, *queue = map + S.MN;
+    const long long nbase = (long long)g * S.MN;
+    const bool act = active ? active[g] != 0 : true;
+    const int n_old = S.n_nodes[g] < S.MN ? S.n_nodes[g] : S.MN;
+    const int pl = played ? played[g] : -3;
+
+    // what search_reset_kernel does, for every game
+    wave_copy(&S.root_board[g], &boards[g], sizeof(HiveBoard), lane);
+    wave_copy(&S.root_hist[g], &hist[g], sizeof(HiveHistory), lane);
+    for (int i = lane; i < S.TT; i += 64) S.tt[(long long)g * S.TT + i] = -1;
+
+    // the child under the played edge: expanded, not a finished game, and really the caller's position
+    int c = -1;
+    if (act && pl >= -1 && n_old > 0 && !S.node_term[nbase]) {
+        const int ne = S.node_nedge[nbase] < EC ? S.node_nedge[nbase] : EC;
+        int edge = -1;
+        for (int k = 0; k < 4 && edge < 0; ++k) {
+            const int e = lane + 64 * k;
+            const unsigned long long m = __ballot(e < ne && (int)S.e_act[nbase * EC + e] == pl);
+            if (m) edge = 64 * k + (int)__builtin_ctzll(m);
+        }
+        if (edge >= 0) {
+            const int ch = S.e_child[nbase * EC + edge];
+            if (ch >= 0 && ch < n_old && !S.node_term[nbase + ch] &&
+                key_equal(reinterpret_cast<const uint32_t *>(&S.node_board[nbase + ch]),
+                          reinterpret_cast<const uint32_t *>(&boards[g]), lane))
+                c = ch;
+        }
+    }
+
+    int kept = 0, visits = 0;
+    if (c >= 0) {
+        // closure of c under e_child >= 0: the transposition table makes the tree a graph with cycles, so nodes are marked
+        for (int i = lane; i < S.MN; i += 64) map[i] = -1;
+        wave_sync();
+        if (lane == 0) { map[c] = 0; queue[0] = c; }
+        wave_sync();
+        kept = 1;
+        for (int head = 0; head < kept && head < S.MN; ++head) {
+            const int node = queue[head];
+            const int ne = S.node_nedge[nbase + node] < EC ? S.node_nedge[nbase + node] : EC;
+            const long long eb = (nbase + node) * EC;
+            for (int k = 0; 64 * k < ne; ++k) {
+                const int e = lane + 64 * k;
+                int ch = e < ne ? S.e_child[eb + e] : -1;
+                if (ch >= n_old) ch = -1;
+                bool want = ch >= 0 && map[ch] < 0;
+                unsigned long long m = __ballot(want);
+                while (m) {                                  // new children in edge order; two edges into one child count once
+                    const int nc = __shfl(ch, (int)__builtin_ctzll(m));
+                    if (lane == 0 && kept < S.MN) { map[nc] = kept; queue[kept] = nc; }
+                    kept++;
+                    if (ch == nc) want = false;
+                    m = __ballot(want);
+                }
+                wave_sync();
+            }
+        }
+        if (kept > S.MN) kept = S.MN;                        // (cannot happen: at most n_old <= MN distinct nodes)
+        visits = S.node_sum_n[nbase + c];
+        if (kept + S.sims_room > S.MN) {                     // no room left for the next search: start fresh, and say so
+            if (lane == 0) S.carry_refused[g] += 1;
+            c = -1;
+        }
+    }
+    if (c < 0) {
+        if (lane == 0) {
+            S.n_nodes[g] = 0;
+            S.root_pending[g] = 0;
+            S.active[g] = act ? 1 : 0;
+            S.carry_kept[g] = 0;
+            S.carry_visits[g] = 0;
+        }
+        return;
+    }
+
+    for (int i = 0; i < kept; ++i) {
+        const long long so = nbase + queue[i], dn = nbase + i;
+        // node 0 takes the caller's records: the key holds neither the turn number nor the history, and the simulation's
+        // env is staged from node 0
+        wave_copy(&D.node_board[dn], i == 0 ? &boards[g] : &S.node_board[so], sizeof(HiveBoard), lane);
+        wave_copy(&D.node_hist[dn], i == 0 ? &hist[g] : &S.node_hist[so], sizeof(HiveHistory), lane);
+        const int ne = S.node_nedge[so] < EC ? S.node_nedge[so] : EC;
+        if (lane == 0) {
+            D.node_nedge[dn] = S.node_nedge[so];
+            D.node_sum_n[dn] = S.node_sum_n[so];
+            D.node_term[dn] = S.node_term[so];
+            D.node_tv[dn] = S.node_tv[so];
+        }
+        for (int e = lane; e < ne; e += 64) {
+            D.e_act[dn * EC + e] = S.e_act[so * EC + e];
+            D.e_p[dn * EC + e] = S.e_p[so * EC + e];
+            D.e_n[dn * EC + e] = S.e_n[so * EC + e];
+            D.e_w[dn * EC + e] = S.e_w[so * EC + e];
+            const int ch = S.e_child[so * EC + e];
+            D.e_child[dn * EC + e] = (ch >= 0 && ch < n_old) ? map[ch] : -1;      // (-2 = in flight: none between searches)
+        }
+    }
+    if (S.merge) {
+        wave_sync();                                         // the cleared table
+        const uint32_t mask = (uint32_t)S.TT - 1u;
+        for (int i = 0; i < kept; ++i) {
+            const HiveBoard *rec = i == 0 ? &boards[g] : &S.node_board[nbase + queue[i]];
+            uint32_t slot = key_hash(reinterpret_cast<const uint32_t *>(rec), lane) & mask;
+            if (lane == 0)                                   // one lane probes and writes: its loads follow its own stores
+                for (int probe = 0; probe < S.TT; ++probe, slot = (slot + 1u) & mask)
+                    if (S.tt[(long long)g * S.TT + slot] < 0) { S.tt[(long long)g * S.TT + slot] = i; break; }
+        }
+    }
+    if (lane == 0) {
+        S.n_nodes[g] = kept;
+        S.root_pending[g] = 0;
+        S.active[g] = 1;
+        S.carry_kept[g] = kept;
+        S.carry_visits[g] = visits;
+    }
+}
+
 }  // namespace hive
 
 // ====================================================================== host side / C ABI
@@ -618,8 +770,10 @@ struct HiveSearch {
     int device = 0;
     hipStream_t stream = nullptr;
     unsigned long long sim = 0;
-    void *pool[40];
+    void *pool[64];
     int npool = 0;
+    NodePool alt{};             // second node pool of hive_search_advance_roots, allocated on first use
+    bool have_alt = false;
 };
 
 template <typename T>
@@ -666,6 +820,12 @@ static int search_alloc(HiveSearch *s, int games, int max_nodes, int slots)
     S_TRY(alloc(s, &d.game_id, (size_t)games));
     S_TRY(alloc(s, &d.kind_hist, (size_t)games * 8));
     S_TRY(hipMemset(d.kind_hist, 0, sizeof(int32_t) * (size_t)games * 8));
+    S_TRY(alloc(s, &d.carry_kept, (size_t)games));
+    S_TRY(alloc(s, &d.carry_visits, (size_t)games));
+    S_TRY(alloc(s, &d.carry_refused, (size_t)games));
+    S_TRY(hipMemset(d.carry_kept, 0, sizeof(int32_t) * (size_t)games));
+    S_TRY(hipMemset(d.carry_visits, 0, sizeof(int32_t) * (size_t)games));
+    S_TRY(hipMemset(d.carry_refused, 0, sizeof(int32_t) * (size_t)games));
     {
         long long *ids = new (std::nothrow) long long[games];
         if (ids == nullptr) return hive::set_error(HIVE_E_DEVICE, "hive_search_create: out of host memory");
@@ -701,6 +861,7 @@ int hive_search_create(int games, int max_nodes, int slots, int device, uint64_t
     if (s == nullptr) return hive::set_error(HIVE_E_DEVICE, "hive_search_create: out of host memory");
     s->device = device;
     s->d.G = games; s->d.MN = max_nodes; s->d.L = slots; s->d.seed = seed;
+    s->d.sims_room = slots + 2;
     s->d.prm = HiveSearchParams{0.7f, 0.25f, 0.3f, 55, HIVE_SEARCH_PUCT, 1.0f};
     int rc = search_alloc(s, games, max_nodes, slots);
     if (rc != HIVE_OK) {            // free whatever was allocated; the caller never sees a partial handle
@@ -746,6 +907,93 @@ int hive_search_set_roots(HiveSearch *s, const HiveBoard *boards, const HiveHist
     hipLaunchKernelGGL(search_reset_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, boards, hist, active);
     S_TRY(hipGetLastError());
     s->sim = 0;                 // simulations are numbered inside one search: part of the noise key (hive_search_set_game_ids)
+    return HIVE_OK;
+}
+
+int hive_search_set_carry_room(HiveSearch *s, int sims_room)
+{
+    if (!s || sims_room < 0) return hive::set_error(HIVE_E_ARG, "hive_search_set_carry_room: bad argument");
+    s->d.sims_room = sims_room;
+    return HIVE_OK;
+}
+
+int hive_search_advance_roots(HiveSearch *s, const int32_t *played, const HiveBoard *boards, const HiveHistory *hist,
+                              const int8_t *active)
+{
+    if (!s || !boards || !hist) return hive::set_error(HIVE_E_ARG, "null argument");
+    S_TRY(hipSetDevice(s->device));
+    SearchDev &d = s->d;
+    // LDS per game: map + queue, 8 bytes per node; four games per workgroup while that fits into 64 KB, else one
+    const size_t per_wave = sizeof(int32_t) * 2 * (size_t)d.MN;
+    const int waves = 4 * per_wave <= 65536 ? 4 : 1;
+    if (per_wave > 65536)
+        return hive::set_error(HIVE_E_ARG, "hive_search_advance_roots: max_nodes above 8192 does not fit the LDS reach mask");
+    if (!s->have_alt) {
+        const size_t GN = (size_t)d.G * d.MN, GE = GN * EC;
+        NodePool &a = s->alt;
+        S_TRY(alloc(s, &a.node_board, GN));
+        S_TRY(alloc(s, &a.node_hist, GN));
+        S_TRY(alloc(s, &a.node_nedge, GN));
+        S_TRY(alloc(s, &a.node_sum_n, GN));
+        S_TRY(alloc(s, &a.node_term, GN));
+        S_TRY(alloc(s, &a.node_tv, GN));
+        S_TRY(alloc(s, &a.e_act, GE));
+        S_TRY(alloc(s, &a.e_p, GE));
+        S_TRY(alloc(s, &a.e_w, GE));
+        S_TRY(alloc(s, &a.e_n, GE));
+        S_TRY(alloc(s, &a.e_child, GE));
+        S_TRY(hipMemset(a.node_term, 0, GN));
+        s->have_alt = true;
+    }
+    hipLaunchKernelGGL(search_advance_kernel, dim3((unsigned)((d.G + waves - 1) / waves)), dim3(64 * waves), waves * per_wave,
+                       s->stream, d, s->alt, played, boards, hist, active);
+    S_TRY(hipGetLastError());
+    // every later launch (stream order) works on the pool the kernel wrote
+    const NodePool old{d.node_board, d.node_hist, d.node_nedge, d.node_sum_n, d.node_term, d.node_tv,
+                       d.e_act, d.e_p, d.e_w, d.e_n, d.e_child};
+    const NodePool &a = s->alt;
+    d.node_board = a.node_board; d.node_hist = a.node_hist; d.node_nedge = a.node_nedge; d.node_sum_n = a.node_sum_n;
+    d.node_term = a.node_term; d.node_tv = a.node_tv; d.e_act = a.e_act; d.e_p = a.e_p; d.e_w = a.e_w; d.e_n = a.e_n;
+    d.e_child = a.e_child;
+    s->alt = old;
+    s->sim = 0;
+    return HIVE_OK;
+}
+
+int hive_search_carry_stats(HiveSearch *s, int32_t *kept_nodes, int32_t *carried_visits, int32_t *refused)
+{
+    if (!s) return hive::set_error(HIVE_E_ARG, "null handle");
+    S_TRY(hipSetDevice(s->device));
+    const size_t bytes = sizeof(int32_t) * (size_t)s->d.G;
+    if (kept_nodes) S_TRY(hipMemcpyAsync(kept_nodes, s->d.carry_kept, bytes, hipMemcpyDeviceToDevice, s->stream));
+    if (carried_visits) S_TRY(hipMemcpyAsync(carried_visits, s->d.carry_visits, bytes, hipMemcpyDeviceToDevice, s->stream));
+    if (refused) S_TRY(hipMemcpyAsync(refused, s->d.carry_refused, bytes, hipMemcpyDeviceToDevice, s->stream));
+    return HIVE_OK;
+}
+
+int hive_search_export_tree(HiveSearch *s, int game, int32_t *n_nodes, HiveBoard *boards, HiveHistory *hist, int32_t *nedge,
+                            int32_t *sum_n, int8_t *term, float *tv, int16_t *e_act, float *e_p, int32_t *e_n, float *e_w,
+                            int32_t *e_child)
+{
+    if (!s || game < 0 || game >= s->d.G) return hive::set_error(HIVE_E_ARG, "hive_search_export_tree: bad argument");
+    S_TRY(hipSetDevice(s->device));
+    const SearchDev &d = s->d;
+    const size_t N = (size_t)d.MN, o = (size_t)game * N;
+#define EXPORT_COPY(dst, src, count)                                                                                    \
+    if (dst) S_TRY(hipMemcpyAsync(dst, src, sizeof(*(dst)) * (count), hipMemcpyDeviceToDevice, s->stream))
+    EXPORT_COPY(n_nodes, d.n_nodes + game, 1);
+    EXPORT_COPY(boards, d.node_board + o, N);
+    EXPORT_COPY(hist, d.node_hist + o, N);
+    EXPORT_COPY(nedge, d.node_nedge + o, N);
+    EXPORT_COPY(sum_n, d.node_sum_n + o, N);
+    EXPORT_COPY(term, d.node_term + o, N);
+    EXPORT_COPY(tv, d.node_tv + o, N);
+    EXPORT_COPY(e_act, d.e_act + o * EC, N * EC);
+    EXPORT_COPY(e_p, d.e_p + o * EC, N * EC);
+    EXPORT_COPY(e_n, d.e_n + o * EC, N * EC);
+    EXPORT_COPY(e_w, d.e_w + o * EC, N * EC);
+    EXPORT_COPY(e_child, d.e_child + o * EC, N * EC);
+#undef EXPORT_COPY
     return HIVE_OK;
 }
 

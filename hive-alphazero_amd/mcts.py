@@ -32,9 +32,14 @@ class TreeSearch:
 
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  c_puct=0.7, noise_eps=0.25, dirichlet_alpha=0.3, max_nodes=None, transpositions=True, mode=PUCT,
-                 virtual_loss=None, max_game_length=None, skip_unread_rows=True, share_equal_leaves=True, reuse_store=0):
+                 virtual_loss=None, max_game_length=None, skip_unread_rows=True, share_equal_leaves=True, reuse_store=0,
+                 keep_tree=False):
         """mode = PUCT: woker/solo_play.py::HivePlayer; mode = UCT: alpha_zero/MCTS_chess.py::UCT_search (plain tree, no
-        noise, no length cap; with one slot the virtual loss is 0 so that W sums exactly like the sequential reference)."""
+        noise, no length cap; with one slot the virtual loss is 0 so that W sums exactly like the sequential reference).
+
+        keep_tree: search(..., played=...) starts from the subtree under the move that was played since the previous
+        search (hive_search_advance_roots) instead of from an empty tree; a tree that would leave fewer than
+        sims + slots + 2 of the max_nodes (default then: 3 * sims + slots + 2) free is dropped (carry_stats)."""
         L = load()
         if L.hive_device_count() <= 0 or not torch.cuda.is_available():
             raise _lib.HiveError(-2, "no HIP device visible: hive_alphazero_amd has no CPU path")
@@ -45,9 +50,13 @@ class TreeSearch:
         self.L = L
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.games, self.sims, self.slots, self.evaluator = games, sims, slots, evaluator
-        self.max_nodes = max_nodes or (sims + slots + 2)
+        self.keep_tree = bool(keep_tree)
+        self.max_nodes = max_nodes or ((3 * sims if self.keep_tree else sims) + slots + 2)
         self._h = ctypes.c_void_p()
         check(L.hive_search_create(games, self.max_nodes, slots, self.device.index, seed, ctypes.byref(self._h)))
+        if self.keep_tree:
+            check(L.hive_search_set_carry_room(self._h, sims + slots + 2))
+            self._unrelated = torch.full((games,), -3, dtype=torch.int32, device=self.device)
         self.mode = mode
         if mode == UCT:
             noise_eps, transpositions = 0.0, False
@@ -158,11 +167,45 @@ class TreeSearch:
         self.evals_launched += n
         return p, v
 
-    def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False):
-        """-> (action int32[games] (-1 pass, -2 inactive/terminal root), policy fp32[games,1584], sum_n int32[games])"""
+    def advance_roots(self, root_boards, root_hist, active=None, played=None):
+        """keep_tree only: the roots of the next search, each tree cut down to the subtree under `played`
+        (hive_search_advance_roots); search() = advance_roots() + run_simulations()."""
+        if not self.keep_tree:
+            raise ValueError("TreeSearch.advance_roots needs keep_tree=True")
+        self._stream()
+        if played is None:
+            played = self._unrelated
+        else:
+            played = torch.as_tensor(played, dtype=torch.int32, device=self.device).contiguous()
+            assert played.numel() == self.games
+        check(self.L.hive_search_advance_roots(self._h, _p(played), _p(root_boards), _p(root_hist), _p(active)))
+
+    def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False, played=None):
+        """-> (action int32[games] (-1 pass, -2 inactive/terminal root), policy fp32[games,1584], sum_n int32[games])
+
+        played (keep_tree only): int32[games], the action that led from the previous search's root to root_boards
+        (-1 pass, -3 unrelated position; None = all -3)."""
         L, G = self.L, self.games
         s = self._stream()
-        check(L.hive_search_set_roots(self._h, _p(root_boards), _p(root_hist), _p(active)))
+        if self.keep_tree:
+            self.advance_roots(root_boards, root_hist, active, played)
+            if keep_root_planes:
+                # a carried root is never a leaf, so the records' feature words come from an encode of the roots themselves
+                # (the kernel code hive_leaf_launch runs on a fresh root; the leaf launches then reuse both buffers)
+                check(L.hive_encode_launch(_p(root_boards), _p(root_hist), G, _p(self.planes), dtype_code(self.plane_dtype),
+                                           HWC, _p(self.workspace), s))
+                self.root_planes = self.workspace[:G * 144].clone()
+                keep_root_planes = False
+        else:
+            if played is not None:
+                raise ValueError("TreeSearch.search: played needs keep_tree=True")
+            check(L.hive_search_set_roots(self._h, _p(root_boards), _p(root_hist), _p(active)))
+        return self.run_simulations(selfplay, keep_root_planes)
+
+    def run_simulations(self, selfplay=False, keep_root_planes=False):
+        """`sims` simulations from the roots as they stand, then the policy: the second half of search()."""
+        L, G = self.L, self.games
+        s = self._stream()
         done = 0
         first = True
         while done < self.sims:
@@ -215,6 +258,32 @@ class TreeSearch:
         check(self.L.hive_search_node_counts(self._h, _p(out)))
         return out
 
+    def carry_stats(self):
+        """(kept_nodes, carried_visits, refused) int32[games]: nodes / root visits the last search started with (0 = fresh
+        tree) and the trees dropped for lack of room in the pool since create (hive_search_carry_stats)."""
+        out = [torch.zeros((self.games,), dtype=torch.int32, device=self.device) for _ in range(3)]
+        self._stream()
+        check(self.L.hive_search_carry_stats(self._h, _p(out[0]), _p(out[1]), _p(out[2])))
+        return out
+
+    def export_tree(self, g):
+        """Game g's tree as numpy arrays (hive_search_export_tree), cut to its n nodes: {"n", "board" uint8[n,64], "hist"
+        uint8[n,384], "nedge", "sum_n", "term", "tv" [n], "act", "p", "n_visits", "w", "child" [n,256]}; of a node's
+        edge rows only the first nedge entries are meaningful."""
+        M, dev = self.max_nodes, self.device
+        spec = [("board", (M, 64), torch.uint8), ("hist", (M, 384), torch.uint8), ("nedge", (M,), torch.int32),
+                ("sum_n", (M,), torch.int32), ("term", (M,), torch.int8), ("tv", (M,), torch.float32),
+                ("act", (M, 256), torch.int16), ("p", (M, 256), torch.float32), ("n_visits", (M, 256), torch.int32),
+                ("w", (M, 256), torch.float32), ("child", (M, 256), torch.int32)]
+        n = torch.zeros((1,), dtype=torch.int32, device=dev)
+        bufs = [torch.zeros(shape, dtype=dt, device=dev) for _, shape, dt in spec]
+        self._stream()
+        check(self.L.hive_search_export_tree(self._h, int(g), _p(n), *[_p(b) for b in bufs]))
+        count = int(n.item())
+        out = {name: b[:count].cpu().numpy() for (name, _, _), b in zip(spec, bufs)}
+        out["n"] = count
+        return out
+
     def transposition_hits(self):
         """int32[games]: descents that continued through a node first reached by another move order."""
         out = torch.zeros((self.games,), dtype=torch.int32, device=self.device)
@@ -232,12 +301,15 @@ class ArenaSearch(TreeSearch):
     across.  hive_arena_join_launch merges the two predictions for the backup.
 
     An evaluator without `accepts_need` (a stub, the library path) gets the whole batch.  `rows_evaluated()` = the rows
-    each network evaluated; `evals_run` is their sum.  reuse_store is refused: the store's key does not hold the network."""
+    each network evaluated; `evals_run` is their sum.  reuse_store is refused: the store's key does not hold the network;
+    keep_tree for the same reason (a kept tree holds the other network's evaluations)."""
 
     def __init__(self, games, sims, evaluator_a, evaluator_b, a_white, device=None, slots=1, seed=0, plane_dtype=None,
                  **options):
         if options.get("reuse_store"):
             raise ValueError("ArenaSearch: reuse_store keeps evaluations by position alone, not by network")
+        if options.get("keep_tree"):
+            raise ValueError("ArenaSearch: keep_tree would hand one network's evaluations to the other, whose ply is next")
         super().__init__(games, sims, evaluator_a, device, slots, seed, plane_dtype, **options)
         self.evaluator_a, self.evaluator_b = evaluator_a, evaluator_b
         assert a_white.dtype == torch.int8 and a_white.numel() == games and a_white.is_cuda and a_white.is_contiguous()
@@ -325,6 +397,8 @@ class SelfPlay:
         self.device = self.env.device
         self.search = TreeSearch(games, sims, evaluator, self.device.index, slots, seed, plane_dtype,
                                  **(search_options or {}))      # e.g. skip_unread_rows / share_equal_leaves = False
+        # keep_tree: the action every slot stepped at the last ply (-3 = none: a new game, or the slot did not move)
+        self._played = (torch.full((games,), -3, dtype=torch.int32, device=self.device) if self.search.keep_tree else None)
         self.keep_records = keep_records
         self.finished = 0
         self.white_wins = self.black_wins = self.draws = 0
@@ -394,6 +468,8 @@ class SelfPlay:
             self.active = (self.game_id >= 0).to(torch.int8)
             self.search.set_game_ids(torch.clamp(self.game_id, min=0))
             self.env.reset(idx)
+            if self._played is not None:
+                self._played[idx.long()] = -3               # the slot's next search belongs to another game
             self._report()
         return nd
 
@@ -463,8 +539,12 @@ class SelfPlay:
         if self._copy_done is not None:
             # the search's policy buffer is rewritten at the end of this search: it waits for the previous ply's record copy
             torch.cuda.current_stream(self.device).wait_event(self._copy_done)
-        action, policy, sum_n = self.search.search(boards, hist, active=self.active, selfplay=True,
-                                                   keep_root_planes=self.keep_records)
+        if self._played is not None:
+            action, policy, sum_n = self.search.search(boards, hist, active=self.active, selfplay=True,
+                                                       keep_root_planes=self.keep_records, played=self._played)
+        else:
+            action, policy, sum_n = self.search.search(boards, hist, active=self.active, selfplay=True,
+                                                       keep_root_planes=self.keep_records)
         if self.keep_records:
             mover = (1 - (boards[:, 33] & 1)).to(torch.int8)
             feat = self.search.root_planes.view(self.games, 144)
@@ -507,6 +587,8 @@ class SelfPlay:
         # the env re-derives the legal masks and refuses anything not in them: the search's edges come
         # from the same kernels, so illegal_count() must stay 0 (asserted by the tests)
         self.env.step(action, sync=False)
+        if self._played is not None:
+            self._played = torch.where(action == -2, torch.full_like(action, -3), action)
         self.plies += 1
         return nd
 

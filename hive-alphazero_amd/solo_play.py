@@ -135,8 +135,39 @@ class HivePlayer:
     def reset(self):
         self._table = {}
 
+    # True: action() keeps the part of the table that lies under env's position instead of emptying it (the sequential
+    # statement of hive_search_advance_roots, include/hive_search.h).  False: the reference, solo_play.py:103-112.
+    keep_tree = False
+
+    def keep_reachable(self, env):
+        """Prune the table to the entries reachable from env's position through visited edges (n > 0), walking copies of
+        env: a finished or length-capped position ends a line, a position only an unvisited edge leads to is forgotten
+        (and evaluated again when it is reached)."""
+        kept = {}
+        todo = [deepcopy(env)]
+        while todo:
+            at = todo.pop()
+            if _terminal_value(at) is not None:
+                continue
+            key = at.state_key
+            entry = self._table.get(key)
+            if entry is None or key in kept:
+                continue
+            kept[key] = entry
+            if entry.moves is None:
+                continue
+            for edge, move in enumerate(entry.moves):
+                if entry.n[edge] > 0:
+                    nxt = deepcopy(at)
+                    nxt.move(move)
+                    todo.append(nxt)
+        self._table = kept
+
     def action(self, env, non_queue=True):
-        self.reset()
+        if self.keep_tree:
+            self.keep_reachable(env)
+        else:
+            self.reset()
         self.max_depth = env.state.turn
         self.main_key_state = env.state_key
         self.search_moves(env)

@@ -69,6 +69,39 @@ int hive_search_set_params(HiveSearch *s, const HiveSearchParams *p);
  * active = int8[games] or NULL: games with active == 0 are skipped by every later call. */
 int hive_search_set_roots(HiveSearch *s, const HiveBoard *boards, const HiveHistory *hist, const int8_t *active);
 
+/* Start the next search from the subtree under the move that was played, instead of from nothing (the reference empties
+ * its tree on every move, solo_play.py:103-112; this is opt-in).  played = int32[games] or NULL: the action id (-1 = pass)
+ * that led from the root of game g's previous search to boards[g]; -3 (and NULL) = an unrelated position.  boards / hist /
+ * active as hive_search_set_roots.
+ * Game g keeps its tree iff it is active, its old root has an edge with that action whose child c exists (>= 0), c is not
+ * a finished game, the position key of c (bytes 0..32 + turn parity, see hive_search_set_transpositions) equals that of
+ * boards[g], and kept + sims_room <= max_nodes (hive_search_set_carry_room).  Every other game is left exactly as
+ * hive_search_set_roots leaves it.
+ * A kept tree holds the nodes reachable from c through expanded edges (child >= 0), c as node 0, renumbered breadth first
+ * in edge order; every node keeps its records, nedge, sum_n, term, tv and its edges' act / p / n / w bit for bit, child is
+ * renumbered.  The one exception: node 0's HiveBoard / HiveHistory become boards[g] / hist[g] -- the key holds neither the
+ * turn number nor the history, and the simulations start from node 0's records.  The transposition table is rebuilt over the
+ * kept nodes.  Out of place: the kept nodes move into a second node pool (allocated by the first call, same size as the
+ * first) and the handle swaps the two.  Any search mode; max_nodes <= 8192. */
+int hive_search_advance_roots(HiveSearch *s, const int32_t *played, const HiveBoard *boards, const HiveHistory *hist,
+                              const int8_t *active);
+
+/* Nodes a kept tree must leave free for the next search (default: slots + 2; a caller that runs `sims` simulations per
+ * search passes sims + slots + 2).  A tree that would leave less is dropped and counted in `refused`. */
+int hive_search_set_carry_room(HiveSearch *s, int sims_room);
+
+/* int32[games] each (any may be NULL): kept_nodes = nodes kept by the last hive_search_advance_roots (0 = fresh tree),
+ * carried_visits = sum_n of the new root carried over by it, refused = trees dropped for lack of room since create. */
+int hive_search_carry_stats(HiveSearch *s, int32_t *kept_nodes, int32_t *carried_visits, int32_t *refused);
+
+/* One game's tree for tests and tools, copied into caller-owned device buffers (any may be NULL): n_nodes = int32[1];
+ * boards / hist / nedge / sum_n / term / tv = [max_nodes]; e_act / e_p / e_n / e_w / e_child = [max_nodes][HIVE_EDGE_CAP].
+ * Only the first n_nodes rows, and of a row's edges the first nedge, are meaningful.  e_child: node index, -1 = not
+ * expanded, -2 = expansion in flight (only between hive_search_select and hive_search_backup). */
+int hive_search_export_tree(HiveSearch *s, int game, int32_t *n_nodes, HiveBoard *boards, HiveHistory *hist, int32_t *nedge,
+                            int32_t *sum_n, int8_t *term, float *tv, int16_t *e_act, float *e_p, int32_t *e_n, float *e_w,
+                            int32_t *e_child);
+
 /* Selection for in-flight slot `slot`: leaf_boards / leaf_hist = [games] records of the positions to
  * evaluate (untouched for games whose path ended in a known terminal node or a collision). */
 int hive_search_select(HiveSearch *s, int slot, HiveBoard *leaf_boards, HiveHistory *leaf_hist);
