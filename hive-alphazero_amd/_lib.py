@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "hive_leaf_store_create", "hive_leaf_store_destroy", "hive_leaf_store_clear", "hive_leaf_store_lookup", "hive_leaf_store_update",
     "hive_leaf_store_stats",
     "hive_replay_create", "hive_replay_destroy", "hive_replay_clear", "hive_replay_stats", "hive_replay_append",
-    "hive_replay_import", "hive_replay_export", "hive_replay_sample",
+    "hive_replay_import", "hive_replay_export", "hive_replay_sample", "hive_replay_append_ranked",
     # include/hive_search.h
     "hive_search_create", "hive_search_destroy", "hive_search_set_stream", "hive_search_set_params",
     "hive_search_set_roots", "hive_search_select", "hive_search_backup", "hive_search_policy",
@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "hive_search_leaf_need",
     "hive_search_advance_roots", "hive_search_set_carry_room", "hive_search_carry_stats", "hive_search_export_tree",
     "hive_arena_split_launch", "hive_arena_join_launch", "hive_arena_opening_launch", "hive_arena_score_launch",
+    "hive_search_set_budgets", "hive_search_draw_budgets", "hive_arena_budget_launch",
     # include/hive_nn.h
     "hive_nn_conv3x3", "hive_nn_resblock", "hive_nn_conv3x3_dt", "hive_nn_resblock_dt", "hive_nn_tower",
     "hive_nn_conv3x3_sel", "hive_nn_resblock_sel", "hive_nn_copy_rows", "hive_nn_tower72", "hive_nn_compact_rows", "hive_nn_tower72_balanced", "hive_nn_tower72_plan_bytes", "hive_nn_conv72", "hive_nn_conv72_add", "hive_nn_conv72_stats",
@@ -142,6 +143,9 @@ def load():
     L.hive_arena_join_launch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.hive_arena_opening_launch.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_uint64, i32, vp, vp]
     L.hive_arena_score_launch.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    L.hive_search_set_budgets.argtypes = [vp, vp, vp]
+    L.hive_search_draw_budgets.argtypes = [ctypes.c_uint64, vp, vp, vp, i32, i32, i32, ctypes.c_uint32, vp, vp, vp, vp]
+    L.hive_arena_budget_launch.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hive_nn_copy_rows.argtypes = [vp, vp, i32, ctypes.c_longlong, vp]
     L.hive_nn_tower72.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.hive_nn_compact_rows.argtypes = [vp, i32, vp, vp, vp]
@@ -169,6 +173,7 @@ def load():
     L.hive_replay_clear.argtypes = [vp, vp]
     L.hive_replay_stats.argtypes = [vp, p64, p64, p64]
     L.hive_replay_append.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, vp]
+    L.hive_replay_append_ranked.argtypes = [vp] * 11 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp]
     L.hive_replay_import.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp]
     L.hive_replay_export.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.hive_replay_sample.argtypes = [vp, vp, u64, u64, u64, i32, i32, i32, vp, vp, vp, vp, vp]

@@ -134,14 +134,22 @@ class Arena:
     """`pairs` pairs of games between evaluator_a and evaluator_b, `games_in_flight` of them in lock step.
 
     arena.run() -> ArenaResult, or `while arena.running(): arena.play_ply()` and `arena.result()`.
-    arena.games[game_id] = (result code, [moves]) for every finished game (keep_moves), arena.results[game_id] = code."""
+    arena.games[game_id] = (result code, [moves]) for every finished game (keep_moves), arena.results[game_id] = code.
+
+    sims_b (default None: both sides search `sims` simulations): the sides search unequally, A with `sims` and B with
+    `sims_b` simulations per move.  The batch then runs max(sims, sims_b) simulations and every game drops out of it after
+    its owner's share (hive_arena_budget_launch at every ply + the search's per-game budgets); rows_evaluated() shows what
+    each side cost.  The first use: how much stronger is one network with 50 simulations than with 10."""
 
     def __init__(self, evaluator_a, evaluator_b, pairs=512, sims=50, slots=1, games_in_flight=1024, seed=0, opening_turns=4,
-                 noise_eps=0.0, pair_ids=None, keep_moves=True, device=None, search_options=None):
+                 noise_eps=0.0, pair_ids=None, keep_moves=True, device=None, search_options=None, sims_b=None):
         import torch
         from . import mcts
         from .batch import BoardBatch
         self.pairs, self.sims, self.seed, self.opening_turns = int(pairs), sims, int(seed), int(opening_turns)
+        self.sims_b = None if sims_b is None else int(sims_b)
+        if self.sims_b is not None and (self.sims_b < 1 or sims < 1):
+            raise ValueError("Arena: sims and sims_b must be at least 1")
         G = self.n = max(1, min(int(games_in_flight), 2 * self.pairs))
         self.env = BoardBatch(G, device)
         dev = self.device = self.env.device
@@ -153,8 +161,10 @@ class Arena:
         self.active = torch.zeros((G,), dtype=torch.int8, device=dev)
         self.a_white = torch.zeros((G,), dtype=torch.int8, device=dev)
         self.pair_id = torch.zeros((G,), dtype=torch.int64, device=dev)
-        self.search = mcts.ArenaSearch(G, sims, evaluator_a, evaluator_b, self.a_white, dev.index, slots, seed,
+        rounds = sims if self.sims_b is None else max(sims, self.sims_b)
+        self.search = mcts.ArenaSearch(G, rounds, evaluator_a, evaluator_b, self.a_white, dev.index, slots, seed,
                                        noise_eps=noise_eps, **(search_options or {}))
+        self.budget = torch.zeros((G,), dtype=torch.int32, device=dev) if self.sims_b is not None else None
         self._assign()
         self.result_codes = torch.zeros((G,), dtype=torch.int8, device=dev)
         self.tally = torch.zeros((8,), dtype=torch.int32, device=dev)
@@ -219,7 +229,11 @@ class Arena:
         turn = boards[:, 33]
         searched = ((self.active != 0) & (turn > self.opening_turns)).to(torch.int8)
         if bool(searched.any().item()):
-            action, _, _ = self.search.search(boards, hist, active=searched, selfplay=False)      # argmax of the visits
+            if self.budget is not None:
+                check(self.L.hive_arena_budget_launch(_p(boards), _p(self.a_white), self.n, self.sims, self.sims_b,
+                                                      _p(self.budget), stream_ptr(self.device)))
+            action, _, _ = self.search.search(boards, hist, active=searched, selfplay=False,      # argmax of the visits
+                                              budgets=self.budget)
             self.searches += 1
         else:
             action = self.search.action.fill_(-2)

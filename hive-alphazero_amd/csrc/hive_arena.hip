@@ -5,6 +5,7 @@
 // thinking: HivePlayer.action evaluates every position of its tree with its own model, whoever is to move in it).
 //   hive_arena_split_launch    the need flags of hive_search_leaf_need, split by owner: each network's tower runs only
 //                              over its own rows
+//   hive_arena_budget_launch   the simulations each game's search gets when the two sides search unequally
 //   hive_arena_join_launch     B's rows of (p, v) copied over A's: one (p, v) pair for hive_search_backup
 //   hive_arena_opening_launch  the uniformly random opening moves (evaluation.py:169,187), keyed on (seed, pair, turn):
 //                              both games of a pair play the same opening
@@ -59,6 +60,16 @@ arena_split_kernel(const HiveBoard *__restrict__ roots, const int8_t *__restrict
         if (rows_a && ba) atomicAdd(rows_a, (unsigned long long)__popcll(ba));
         if (rows_b && bb) atomicAdd(rows_b, (unsigned long long)__popcll(bb));
     }
+}
+
+// one lane per game
+__global__ void __launch_bounds__(256)
+arena_budget_kernel(const HiveBoard *__restrict__ roots, const int8_t *__restrict__ a_white, int games, int sims_a, int sims_b,
+                    int32_t *__restrict__ budget)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= games) return;
+    budget[g] = owner_is_a(roots, a_white, g) ? sims_a : sims_b;
 }
 
 // one wave per row
@@ -151,6 +162,17 @@ extern "C" int hive_arena_split_launch(const HiveBoard *root_boards, const int8_
     hipLaunchKernelGGL(arena_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, root_boards, a_white,
                        need, games, n, need_a, need_b, reinterpret_cast<unsigned long long *>(rows_a),
                        reinterpret_cast<unsigned long long *>(rows_b));
+    ARENA_TRY(hipGetLastError());
+    return HIVE_OK;
+}
+
+extern "C" int hive_arena_budget_launch(const HiveBoard *root_boards, const int8_t *a_white, int games, int sims_a, int sims_b,
+                                        int32_t *budget, void *stream)
+{
+    if (!root_boards || !a_white || !budget || games <= 0 || sims_a < 0 || sims_b < 0)
+        return hive::set_error(HIVE_E_ARG, "hive_arena_budget_launch: bad argument");
+    hipLaunchKernelGGL(arena_budget_kernel, dim3((unsigned)((games + 255) / 256)), dim3(256), 0, (hipStream_t)stream, root_boards,
+                       a_white, games, sims_a, sims_b, budget);
     ARENA_TRY(hipGetLastError());
     return HIVE_OK;
 }

@@ -84,12 +84,18 @@ replay_write_kernel(Ring ring, long long head, long long skip, long long rows, l
                     const unsigned long long *__restrict__ feat, const uint32_t *__restrict__ hist, const uint8_t *__restrict__ meta,
                     const int16_t *__restrict__ pol_idx, const float *__restrict__ pol_val, const long long *__restrict__ pol_ptr,
                     const int32_t *__restrict__ pol_cnt, const long long *__restrict__ game_ptr, const int8_t *__restrict__ game_val,
-                    const float *__restrict__ values, const float *__restrict__ discount)
+                    const float *__restrict__ values, const float *__restrict__ discount, const long long *__restrict__ rank,
+                    long long rank_skip)
 {
     __shared__ int later;                                  // later moves of the row's side in its game
     const int tid = threadIdx.x;
     for (long long i = skip + blockIdx.x; i < rows; i += gridDim.x) {
-        const size_t slot = (size_t)((head + i) % ring.capacity);
+        // rank (hive_replay_append_ranked): the row's place among the rows that are kept, -1 = not a row of the window; of more
+        // kept rows than the ring holds the first rank_skip are left out (the same for the whole workgroup).  The rows of its
+        // game below are walked whether they are kept or not
+        const long long dest = rank != nullptr ? rank[i] : i;
+        if (dest < rank_skip) continue;
+        const size_t slot = (size_t)((head + dest) % ring.capacity);
         if (tid < kCells) ring.feat[slot * kCells + tid] = feat[i * kCells + tid];
         else if (tid < kCells + kHistWords) ring.hist[slot * kHistWords + (tid - kCells)] = hist[i * kHistWords + (tid - kCells)];
         const int stride = PACKED ? 3 : 4;
@@ -341,9 +347,40 @@ extern "C" int hive_replay_append(HiveReplay *r, const uint64_t *feat, const uin
     hipLaunchKernelGGL((replay_write_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, ring_of(r), r->head, skip,
                        (long long)rows, (long long)games, reinterpret_cast<const unsigned long long *>(feat), hist, meta, pol_idx,
                        pol_val, reinterpret_cast<const long long *>(pol_ptr), (const int32_t *)nullptr,
-                       reinterpret_cast<const long long *>(game_ptr), game_val, (const float *)nullptr, r->discount);
+                       reinterpret_cast<const long long *>(game_ptr), game_val, (const float *)nullptr, r->discount,
+                       (const long long *)nullptr, 0ll);
     REPLAY_TRY(hipGetLastError());
     advance(r, rows);
+    return HIVE_OK;
+}
+
+extern "C" int hive_replay_append_ranked(HiveReplay *r, const uint64_t *feat, const uint32_t *hist, const uint8_t *meta,
+                                         const int16_t *pol_idx, const float *pol_val, const int64_t *pol_ptr, const int64_t *game_ptr,
+                                         const int8_t *game_val, const int64_t *pol_ptr_host, const int64_t *rank, int64_t rows,
+                                         int64_t games, int64_t kept, void *stream)
+{
+    if (!r) return hive::set_error(HIVE_E_ARG, "hive_replay_append_ranked: null handle");
+    if (rows < 0 || games < 0 || kept < 0 || kept > rows) return hive::set_error(HIVE_E_ARG, "hive_replay_append_ranked: bad count");
+    if (rows == 0 || kept == 0) return HIVE_OK;
+    if (!feat || !hist || !meta || !pol_ptr || !game_ptr || !game_val || !pol_ptr_host || !rank || games == 0)
+        return hive::set_error(HIVE_E_ARG, "hive_replay_append_ranked: null pointer (or no game) with rows > 0");
+    long long entries = 0;
+    for (int64_t i = 0; i < rows; ++i) {
+        const long long c = (long long)(pol_ptr_host[i + 1] - pol_ptr_host[i]);
+        if (c < 0 || c > HIVE_LIST_CAP)
+            return hive::set_error(HIVE_E_ARG, "hive_replay_append_ranked: row " + std::to_string(i) + " has " + std::to_string(c) +
+                                                   " policy entries (0 .. " + std::to_string(HIVE_LIST_CAP) + ")");
+        entries += c;
+    }
+    if (entries > 0 && (!pol_idx || !pol_val)) return hive::set_error(HIVE_E_ARG, "hive_replay_append_ranked: null policy arrays");
+    const unsigned blocks = (unsigned)std::min<long long>(rows, kReplayMaxBlocks);
+    hipLaunchKernelGGL((replay_write_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, ring_of(r), r->head, 0ll,
+                       (long long)rows, (long long)games, reinterpret_cast<const unsigned long long *>(feat), hist, meta, pol_idx,
+                       pol_val, reinterpret_cast<const long long *>(pol_ptr), (const int32_t *)nullptr,
+                       reinterpret_cast<const long long *>(game_ptr), game_val, (const float *)nullptr, r->discount,
+                       reinterpret_cast<const long long *>(rank), (long long)(kept > r->capacity ? kept - r->capacity : 0));
+    REPLAY_TRY(hipGetLastError());
+    advance(r, kept);
     return HIVE_OK;
 }
 
@@ -361,7 +398,7 @@ extern "C" int hive_replay_import(HiveReplay *r, const uint64_t *feat, const uin
     hipLaunchKernelGGL((replay_write_kernel<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, ring_of(r), r->head, skip,
                        (long long)rows, 0ll, reinterpret_cast<const unsigned long long *>(feat), hist, meta, pol_idx, pol_val,
                        (const long long *)nullptr, pol_cnt, (const long long *)nullptr, (const int8_t *)nullptr, values,
-                       r->discount);
+                       r->discount, (const long long *)nullptr, 0ll);
     REPLAY_TRY(hipGetLastError());
     advance(r, rows);
     return HIVE_OK;

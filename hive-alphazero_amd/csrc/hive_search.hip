@@ -46,6 +46,8 @@ struct SearchDev {
     int32_t *kind_hist;                            // [G][8] leaves by LeafKind since create (statistics)
     int32_t *carry_kept, *carry_visits, *carry_refused;   // [G] hive_search_carry_stats
     int sims_room;                                 // nodes a carried tree must leave free (hive_search_set_carry_room)
+    const int32_t *budget;                         // [G] simulations of this search per game, or nullptr (hive_search_set_budgets)
+    const int8_t *quiet;                           // [G] != 0: no root noise for that game, or nullptr
 };
 
 // the node arrays of one pool: hive_search_advance_roots moves the kept subtrees from the handle's pool into a second one
@@ -208,7 +210,9 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
     if (g >= S.G) return;
     const long long sg = (long long)slot * S.G + g;
     int32_t *pnode = S.path_node + sg * S.MN, *pedge = S.path_edge + sg * S.MN;
-    if (!S.active[g]) { if (lane == 0) { S.leaf_kind[sg] = LEAF_NONE; S.path_len[sg] = 0; } return; }
+    // a game whose budget is spent sits the rest of the search out exactly like an inactive one: no leaf, no virtual loss
+    const bool spent = S.budget != nullptr && (long long)sim >= (long long)S.budget[g];
+    if (!S.active[g] || spent) { if (lane == 0) { S.leaf_kind[sg] = LEAF_NONE; S.path_len[sg] = 0; } return; }
 
     if (S.n_nodes[g] == 0) {
         // first simulation of a search only evaluates the root (solo_play.py:188-197)
@@ -233,6 +237,7 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     int node = 0, depth = 0, kind = LEAF_NONE, leafnode = 0, leafedge = 0;
     const unsigned root_turn = reinterpret_cast<const uint8_t *>(st)[33];
+    const bool quiet = S.quiet != nullptr && S.quiet[g] != 0;
     while (true) {
         if (S.node_term[nbase + node]) { kind = LEAF_TERMINAL; leafnode = node; break; }          // game over (solo_play.py:169-180)
         if ((int)reinterpret_cast<const uint8_t *>(st)[33] >= S.prm.max_game_length) { kind = LEAF_CAPDRAW; break; }   // :181-183
@@ -244,7 +249,7 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
         const float xx = sqrtf((float)S.node_sum_n[nbase + node] + 1.0f);
         // fresh Dirichlet noise on the root priors for every simulation (solo_play.py:322-323)
         float noise[4] = {0.f, 0.f, 0.f, 0.f};
-        const bool noisy = depth == 0 && !uct && S.prm.noise_eps > 0.f;
+        const bool noisy = depth == 0 && !uct && S.prm.noise_eps > 0.f && !quiet;
         if (noisy)
             wave_dirichlet(noise, ne, S.prm.dirichlet_alpha, S.seed, S.game_id[g], root_turn, sim, slot, lane);
         float best = -3.0e38f;
@@ -613,6 +618,26 @@ search_noise_kernel(unsigned long long seed, long long first_game, unsigned turn
     }
 }
 
+// hive_search_draw_budgets: one thread per game.  Full or fast ply: a pure function of (seed, game id, root turn) -- the
+// first output of the generator keyed like every other draw here, on a stream constant of its own
+constexpr unsigned long long kBudgetStream = 0x8CB92BA72F3D8DD7ull;
+__global__ void __launch_bounds__(256)
+search_draw_budgets_kernel(unsigned long long seed, const long long *__restrict__ game_id, const HiveBoard *__restrict__ roots,
+                           const int8_t *__restrict__ active, int n, int full_sims, int fast_sims, uint32_t full_threshold,
+                           int32_t *__restrict__ budget, int8_t *__restrict__ quiet, int8_t *__restrict__ full)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const bool on = active ? active[g] != 0 : true;
+    const unsigned long long x = splitmix(Rng(seed ^ kBudgetStream, (unsigned long long)game_id[g],
+                                              (unsigned long long)roots[g].turn, 0ull).s);
+    // a saturated threshold (p_full = 1) is "always"
+    const bool f = on && (full_threshold == 0xFFFFFFFFu || (uint32_t)(x >> 32) < full_threshold);
+    budget[g] = on ? (f ? full_sims : fast_sims) : 0;
+    if (quiet) quiet[g] = (on && !f) ? 1 : 0;
+    if (full) full[g] = f ? 1 : 0;
+}
+
 // lanes of one wave see each other's LDS / global writes made before this point
 __device__ __forceinline__ void wave_sync()
 {
@@ -907,6 +932,28 @@ int hive_search_set_roots(HiveSearch *s, const HiveBoard *boards, const HiveHist
     hipLaunchKernelGGL(search_reset_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, boards, hist, active);
     S_TRY(hipGetLastError());
     s->sim = 0;                 // simulations are numbered inside one search: part of the noise key (hive_search_set_game_ids)
+    return HIVE_OK;
+}
+
+int hive_search_set_budgets(HiveSearch *s, const int32_t *budget, const int8_t *quiet)
+{
+    if (!s) return hive::set_error(HIVE_E_ARG, "null handle");
+    if (!budget && quiet) return hive::set_error(HIVE_E_ARG, "hive_search_set_budgets: quiet without budget");
+    s->d.budget = budget;
+    s->d.quiet = quiet;
+    return HIVE_OK;
+}
+
+int hive_search_draw_budgets(uint64_t seed, const int64_t *game_id, const HiveBoard *root_boards, const int8_t *active, int n,
+                             int full_sims, int fast_sims, uint32_t full_threshold, int32_t *budget, int8_t *quiet, int8_t *full,
+                             void *stream)
+{
+    if (!game_id || !root_boards || !budget || n <= 0 || full_sims < 0 || fast_sims < 0)
+        return hive::set_error(HIVE_E_ARG, "hive_search_draw_budgets: bad argument");
+    hipLaunchKernelGGL(search_draw_budgets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, reinterpret_cast<const long long *>(game_id), root_boards, active, n, full_sims,
+                       fast_sims, full_threshold, budget, quiet, full);
+    S_TRY(hipGetLastError());
     return HIVE_OK;
 }
 

@@ -20,6 +20,34 @@ LEAF_KINDS = ("unused", "root_evaluated", "expanded_evaluated", "known_finished_
               "new_finished_or_capped", "already_created_in_flight")
 
 
+BUDGET_STREAM = 0x8CB92BA72F3D8DD7      # stream constant of hive_search_draw_budgets (include/hive_search.h)
+
+
+def full_threshold(p_full):
+    """floor(p_full * 2^32) saturated to 32 bits: what hive_search_draw_budgets compares the draw with (0xFFFFFFFF = always)."""
+    if not 0.0 <= p_full <= 1.0:
+        raise ValueError("p_full must lie in [0, 1]")
+    return min(int(p_full * 4294967296.0), 0xFFFFFFFF)
+
+
+def playout_cap_draw(seed, game_ids, turns, p_full):
+    """bool[n]: is the ply of game game_ids[i] at root turn turns[i] searched in full?  The numpy restatement of
+    hive_search_draw_budgets (no GPU): x = the first output of csrc/hive_rng.hpp's generator keyed by (seed ^ BUDGET_STREAM,
+    game id, turn, 0); full iff (x >> 32) < floor(p_full * 2^32), and always at p_full = 1 (the saturated threshold)."""
+    import numpy as np
+    from .replay import _M64, _splitmix
+    thr = full_threshold(p_full)
+    if thr == 0xFFFFFFFF:
+        return np.ones(len(game_ids), dtype=bool)
+    with np.errstate(over="ignore"):
+        a = np.asarray(game_ids, dtype=np.int64).astype(np.uint64)
+        b = np.asarray(turns, dtype=np.int64).astype(np.uint64)
+        key = np.uint64((int(seed) ^ BUDGET_STREAM) & _M64)
+        s = _splitmix(key ^ _splitmix(a * np.uint64(0x100000001B3) + _splitmix(b * np.uint64(0x9E3779B1))))
+        x = _splitmix(s)
+    return (x >> np.uint64(32)) < np.uint64(thr)
+
+
 class _Params(ctypes.Structure):
     _fields_ = [("c_puct", ctypes.c_float), ("noise_eps", ctypes.c_float), ("dirichlet_alpha", ctypes.c_float),
                 ("max_game_length", ctypes.c_int32), ("mode", ctypes.c_int32), ("virtual_loss", ctypes.c_float)]
@@ -84,6 +112,7 @@ class TreeSearch:
         self.action = torch.zeros((games,), dtype=torch.int32, device=dev)
         self.sum_n = torch.zeros((games,), dtype=torch.int32, device=dev)
         self.root_planes = None
+        self._budgets = self._quiet = None      # per-game budgets of the current search (the handle keeps their addresses)
         # rows of the leaf batch whose prediction the backup never reads (finished games, length cap, collisions, idle
         # trees: the reference does not call its model for them either, solo_play.py:169-197) are skipped by an evaluator
         # that can (InferenceNet: its tower kernels take the flags); evals_run counts the rows that were evaluated
@@ -180,13 +209,41 @@ class TreeSearch:
             assert played.numel() == self.games
         check(self.L.hive_search_advance_roots(self._h, _p(played), _p(root_boards), _p(root_hist), _p(active)))
 
-    def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False, played=None):
+    def set_budgets(self, budgets=None, quiet=None):
+        """Per-game simulation budgets of the searches from now on (hive_search_set_budgets): budgets int32[games], quiet
+        int8[games] (1 = no root noise for that game), device tensors that this object keeps alive; None, None = off.
+        `sims` stays the number of simulations the batch runs; a budget given on the host is checked against it (a device
+        tensor is taken as it is: a budget above `sims` then simply ends at `sims`)."""
+        if budgets is None:
+            if quiet is not None:
+                raise ValueError("TreeSearch: quiet needs budgets")
+        else:
+            if not (isinstance(budgets, torch.Tensor) and budgets.is_cuda):
+                host = torch.as_tensor(budgets).reshape(-1)
+                if host.numel() and int(host.max()) > self.sims:
+                    raise ValueError(f"TreeSearch: a budget of {int(host.max())} simulations exceeds sims={self.sims}")
+            budgets = torch.as_tensor(budgets).to(device=self.device, dtype=torch.int32).contiguous()
+            assert budgets.numel() == self.games
+            if quiet is not None:
+                quiet = torch.as_tensor(quiet).to(device=self.device, dtype=torch.int8).contiguous()
+                assert quiet.numel() == self.games
+        self._budgets, self._quiet = budgets, quiet
+        check(self.L.hive_search_set_budgets(self._h, _p(budgets), _p(quiet)))
+
+    def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False, played=None, budgets=None,
+               quiet=None):
         """-> (action int32[games] (-1 pass, -2 inactive/terminal root), policy fp32[games,1584], sum_n int32[games])
 
         played (keep_tree only): int32[games], the action that led from the previous search's root to root_boards
-        (-1 pass, -3 unrelated position; None = all -3)."""
+        (-1 pass, -3 unrelated position; None = all -3).
+        budgets / quiet: set_budgets for this search -- game g takes part in the first budgets[g] of the `sims` simulations
+        and ends with the tree TreeSearch(sims=budgets[g]) would have given it; None = every game gets all of them."""
         L, G = self.L, self.games
         s = self._stream()
+        if budgets is not None or self._budgets is not None:
+            self.set_budgets(budgets, quiet)
+        elif quiet is not None:
+            raise ValueError("TreeSearch: quiet needs budgets")
         if self.keep_tree:
             self.advance_roots(root_boards, root_hist, active, played)
             if keep_root_planes:
@@ -333,9 +390,9 @@ class ArenaSearch(TreeSearch):
         a, b = self.rows.cpu().tolist()
         return int(a), int(b)
 
-    def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False):
+    def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False, budgets=None, quiet=None):
         self._roots = root_boards
-        out = super().search(root_boards, root_hist, active, selfplay, keep_root_planes)
+        out = super().search(root_boards, root_hist, active, selfplay, keep_root_planes, budgets=budgets, quiet=quiet)
         torch.sum(self.rows, 0, keepdim=True, out=self.evals_run)
         return out
 
@@ -385,14 +442,36 @@ class SelfPlay:
     container the caller drains: True keeps the batches (`drain_finished_packed()`; what SelfPlayWorker's children send
     to the parent), False expands every game of a batch into `finished_games` as (value_white, plies, game_id)
     (`drain_finished()`; per-row tuples with dense policies, for a few hundred games).  More than `max_finished_kept`
-    undrained games are dropped and counted (`dropped_games`, one warning)."""
+    undrained games are dropped and counted (`dropped_games`, one warning).
+
+    playout_cap = {"full": 50, "fast": 10, "p_full": 0.25, "quiet_fast": True} (default None: every ply gets `sims`
+    simulations): playout-cap randomisation.  Every ply of every game is drawn full (probability p_full) or fast by
+    hive_search_draw_budgets from (seed, game id, turn) and searched with that many of the `sims` = max(full, fast)
+    simulations; a fast ply is searched without root noise (quiet_fast, default True).  Move selection is unchanged.  A fast
+    ply stays a row of its game, marked 0 in the packed batch's `full` key (records.FULL_KEY): datasets and the replay
+    window take the rows marked 1.  With keep_records this needs packed_records=True -- the 6-tuples of the row-wise
+    route have no room for the flag.  p_full = 1 with full == fast == sims plays the plain engine's games bit for bit."""
 
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  keep_records=True, game_ids=None, max_finished_kept=1024, report_every=0, log=print, packed_records=False,
-                 search_options=None):
+                 search_options=None, playout_cap=None):
         import itertools
         from .batch import BoardBatch
-        self.games, self.sims = games, sims
+        self.playout_cap = None
+        if playout_cap is not None:
+            cap = dict(playout_cap)
+            unknown = set(cap) - {"full", "fast", "p_full", "quiet_fast"}
+            if unknown or not {"full", "fast", "p_full"} <= set(cap):
+                raise ValueError("playout_cap takes full, fast, p_full and optionally quiet_fast")
+            cap["full"], cap["fast"], cap["quiet_fast"] = int(cap["full"]), int(cap["fast"]), bool(cap.get("quiet_fast", True))
+            if cap["full"] < 1 or cap["fast"] < 1 or sims != max(cap["full"], cap["fast"]):
+                raise ValueError("playout_cap: full and fast must be at least 1 and sims must equal max(full, fast)")
+            cap["threshold"] = full_threshold(float(cap["p_full"]))
+            if keep_records and not packed_records:
+                raise ValueError("playout_cap with keep_records needs packed_records=True: the per-row tuples cannot carry "
+                                 "the full / fast flag")
+            self.playout_cap = cap
+        self.games, self.sims, self.seed = games, sims, int(seed)
         self.env = BoardBatch(games, device)
         self.device = self.env.device
         self.search = TreeSearch(games, sims, evaluator, self.device.index, slots, seed, plane_dtype,
@@ -421,6 +500,10 @@ class SelfPlay:
         # per-ply record copies leave on a side stream into pinned host buffers while the next search runs
         self._copy_stream = torch.cuda.Stream(self.device) if keep_records else None
         self._copy_done = None       # event of the newest record copy (the log's entries are valid once it has passed)
+        if self.playout_cap is not None:
+            self.budget = torch.zeros((games,), dtype=torch.int32, device=self.device)
+            self.full = torch.zeros((games,), dtype=torch.int8, device=self.device)
+            self.quiet = torch.zeros((games,), dtype=torch.int8, device=self.device) if self.playout_cap["quiet_fast"] else None
 
     def stagger(self, seed=0):
         """Spread the games over plies 0..53 with uniformly random legal moves so that a timed window
@@ -539,12 +622,17 @@ class SelfPlay:
         if self._copy_done is not None:
             # the search's policy buffer is rewritten at the end of this search: it waits for the previous ply's record copy
             torch.cuda.current_stream(self.device).wait_event(self._copy_done)
+        extra = {}
         if self._played is not None:
-            action, policy, sum_n = self.search.search(boards, hist, active=self.active, selfplay=True,
-                                                       keep_root_planes=self.keep_records, played=self._played)
-        else:
-            action, policy, sum_n = self.search.search(boards, hist, active=self.active, selfplay=True,
-                                                       keep_root_planes=self.keep_records)
+            extra["played"] = self._played
+        if self.playout_cap is not None:
+            cap = self.playout_cap
+            check(self.search.L.hive_search_draw_budgets(ctypes.c_uint64(self.seed & (2 ** 64 - 1)), _p(self.game_id), _p(boards),
+                                                         _p(self.active), self.games, cap["full"], cap["fast"], cap["threshold"],
+                                                         _p(self.budget), _p(self.quiet), _p(self.full), stream_ptr(self.device)))
+            extra["budgets"], extra["quiet"] = self.budget, self.quiet
+        action, policy, sum_n = self.search.search(boards, hist, active=self.active, selfplay=True,
+                                                   keep_root_planes=self.keep_records, **extra)
         if self.keep_records:
             mover = (1 - (boards[:, 33] & 1)).to(torch.int8)
             feat = self.search.root_planes.view(self.games, 144)
@@ -557,6 +645,8 @@ class SelfPlay:
             # row per ply in the game loop itself; here that costs the engine nothing but the PCIe transfer)
             moved = action != -2
             src = {"feat": feat, "policy": policy, "boards": boards, "hist": hist, "moved": moved}
+            if self.playout_cap is not None:
+                src["full"] = self.full             # (redrawn by the next ply, which waits for this copy like the policy buffer)
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream(self.device))
             prev_copy = self._copy_done

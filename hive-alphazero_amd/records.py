@@ -103,6 +103,22 @@ def rows_from_game(entry):
 
 
 PACKED_KEYS = ("feat", "hist", "meta", "pol_idx", "pol_val", "pol_ptr", "game_ptr", "game_val", "game_id")
+# The one OPTIONAL key of a packed batch: full u8[R], 1 = a training row, 0 = a ply that only moved its game along (the
+# fast plies of mcts.SelfPlay(playout_cap=...)).  Such a row stays a row of its game -- the value rule counts the moves of
+# a side still to come -- but is no row of a dataset or of the replay window.  A batch without the key is all ones.
+FULL_KEY = "full"
+
+
+def _packed_keys(packed):
+    """The keys a container carries for this batch: PACKED_KEYS, and the optional one when the batch has it."""
+    return PACKED_KEYS + ((FULL_KEY,) if FULL_KEY in packed else ())
+
+
+def training_rows(packed):
+    """int64[N]: the rows of a packed batch that are training rows, ascending (all of them without the `full` key)."""
+    if FULL_KEY not in packed:
+        return np.arange(len(packed["meta"]), dtype=np.int64)
+    return np.flatnonzero(np.asarray(packed[FULL_KEY]) != 0).astype(np.int64)
 
 
 def pack_games(games):
@@ -144,14 +160,18 @@ def slice_packed(packed, lo, hi):
     """Games lo .. hi-1 of a packed batch as a packed batch of their own."""
     r0, r1 = int(packed["game_ptr"][lo]), int(packed["game_ptr"][hi])
     p0, p1 = int(packed["pol_ptr"][r0]), int(packed["pol_ptr"][r1])
-    return {"feat": packed["feat"][r0:r1], "hist": packed["hist"][r0:r1], "meta": packed["meta"][r0:r1],
-            "pol_idx": packed["pol_idx"][p0:p1], "pol_val": packed["pol_val"][p0:p1],
-            "pol_ptr": packed["pol_ptr"][r0:r1 + 1] - p0, "game_ptr": packed["game_ptr"][lo:hi + 1] - r0,
-            "game_val": packed["game_val"][lo:hi], "game_id": packed["game_id"][lo:hi]}
+    out = {"feat": packed["feat"][r0:r1], "hist": packed["hist"][r0:r1], "meta": packed["meta"][r0:r1],
+           "pol_idx": packed["pol_idx"][p0:p1], "pol_val": packed["pol_val"][p0:p1],
+           "pol_ptr": packed["pol_ptr"][r0:r1 + 1] - p0, "game_ptr": packed["game_ptr"][lo:hi + 1] - r0,
+           "game_val": packed["game_val"][lo:hi], "game_id": packed["game_id"][lo:hi]}
+    if FULL_KEY in packed:
+        out[FULL_KEY] = packed[FULL_KEY][r0:r1]
+    return out
 
 
 def concat_packed(batches):
-    """Several packed batches -> one (game order = batch order)."""
+    """Several packed batches -> one (game order = batch order).  If any of them has the `full` key the result has it, and a
+    batch without it counts as all ones."""
     batches = list(batches)
     if len(batches) == 1:
         return batches[0]
@@ -164,6 +184,9 @@ def concat_packed(batches):
             parts.append(b[key][1:] + base)
             base += len(b[unit])
         out[key] = np.concatenate(parts)
+    if any(FULL_KEY in b for b in batches):
+        out[FULL_KEY] = np.concatenate([np.asarray(b[FULL_KEY], dtype=np.uint8) if FULL_KEY in b
+                                        else np.ones(len(b["meta"]), dtype=np.uint8) for b in batches])
     return out
 
 
@@ -243,7 +266,7 @@ def save_packed(path, packed, level=1):
     SelfPlayWorker parent compress ~55 MB/s of records (tests/test_host_cpu.py, parent-ingest soak)."""
     import zipfile
     with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=level) as z:
-        for k in PACKED_KEYS:
+        for k in _packed_keys(packed):
             with z.open(k + ".npy", "w", force_zip64=True) as f:
                 np.lib.format.write_array(f, np.ascontiguousarray(packed[k]), allow_pickle=False)
     return path
@@ -260,7 +283,7 @@ def packed_to_blob(packed, path):
     queue cost the parent's main thread ~0.5-1.2 s of pipe reads and unpickling per lock-step wave; mapped from a tmpfs
     file it costs a millisecond, and the writer threads compress straight out of the mapping."""
     layout, off = [], 0
-    for k in PACKED_KEYS:
+    for k in _packed_keys(packed):
         a = np.ascontiguousarray(packed[k])
         layout.append((k, a.dtype.str, tuple(a.shape), off))
         off += (a.nbytes + 63) // 64 * 64
@@ -290,7 +313,7 @@ def packed_from_blob(path, layout, unlink=True):
 
 def load_packed(path):
     with np.load(path) as z:                      # plain arrays only: nothing in the file is executed
-        return {k: z[k] for k in PACKED_KEYS}
+        return {k: z[k] for k in PACKED_KEYS + ((FULL_KEY,) if FULL_KEY in z.files else ())}
 
 
 def load_games(path):
@@ -322,11 +345,15 @@ def packed_values(packed):
 
 def dataset_from_packed(packed):
     """What woker/optimize.py:42-65 builds from the JSON rows, straight from a packed batch: (states float32 [N,12,12,56],
-    policies float32 [N,1584], values float32 [N] = packed_values)."""
+    policies float32 [N,1584], values float32 [N] = packed_values).  With the `full` key: the rows marked 1 only, their
+    values still computed over all rows of their games."""
     meta, csr = packed["meta"], (packed["pol_ptr"], packed["pol_idx"], packed["pol_val"])
+    rows = training_rows(packed).tolist()
     states = [unpack_features(packed["feat"][r], int(meta[r, 1]), history_planes(packed["hist"][r], int(meta[r, 0]))).astype(np.float32)
-              for r in range(len(meta))]
-    return np.stack(states), np.stack([_dense_row(csr, r) for r in range(len(meta))]), packed_values(packed)
+              for r in rows]
+    if not rows:
+        return np.zeros((0, 12, 12, 56), np.float32), np.zeros((0, 1584), np.float32), np.zeros((0,), np.float32)
+    return np.stack(states), np.stack([_dense_row(csr, r) for r in rows]), packed_values(packed)[rows]
 
 
 def dataset_from_games(games):
@@ -369,10 +396,22 @@ def dataset_tensors_gpu_packed(packed, device=None, dtype=None, layout="chw"):
     SelfPlay.drain_finished_packed): the packed features, history words and turn bytes go up as they are (1.5 KB per row),
     the env's plane writer widens them, the sparse policies are scattered into the dense matrix on the GPU -- what a trainer
     that keeps up with the self-play GPUs uses.  -> (states [N,56,12,12] ("chw", what ChessNet takes) or [N,12,12,56],
-    policies float32 [N,1584], values float32 [N] = packed_values) on `device`."""
+    policies float32 [N,1584], values float32 [N] = packed_values) on `device`.  With the `full` key: the rows marked 1 only,
+    their values still computed over all rows of their games."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
     dtype = dtype or torch.float32
+    values = packed_values(packed)
+    if FULL_KEY in packed:
+        keep = training_rows(packed)
+        ptr = np.asarray(packed["pol_ptr"], dtype=np.int64)
+        c = ptr[keep + 1] - ptr[keep]
+        new_ptr = np.zeros(len(keep) + 1, dtype=np.int64)
+        np.cumsum(c, out=new_ptr[1:])
+        src = np.repeat(ptr[keep] - new_ptr[:-1], c) + np.arange(int(new_ptr[-1]))
+        packed = {"feat": packed["feat"][keep], "hist": packed["hist"][keep], "meta": packed["meta"][keep],
+                  "pol_ptr": new_ptr, "pol_idx": packed["pol_idx"][src], "pol_val": packed["pol_val"][src]}
+        values = values[keep]
     n = len(packed["meta"])
     if n == 0:                      # nothing to widen (hive_expand_launch refuses n <= 0)
         shape = (0, 56, 12, 12) if layout == "chw" else (0, 12, 12, 56)
@@ -383,7 +422,7 @@ def dataset_tensors_gpu_packed(packed, device=None, dtype=None, layout="chw"):
     flat = torch.from_numpy(rows * 1584 + packed["pol_idx"].astype(np.int64)).to(dev)
     policies = torch.zeros((n * 1584,), dtype=torch.float32, device=dev)
     policies[flat] = torch.from_numpy(np.ascontiguousarray(packed["pol_val"])).to(dev)
-    return planes, policies.view(n, 1584), torch.from_numpy(packed_values(packed)).to(dev)
+    return planes, policies.view(n, 1584), torch.from_numpy(np.ascontiguousarray(values)).to(dev)
 
 
 def dataset_tensors_gpu(games, device=None, dtype=None, layout="chw"):
@@ -409,13 +448,17 @@ class PlyLog:
         self.unlogged = [False] * slots      # opening plies of this slot's game were not logged
         self.max_finished_kept = max_finished_kept
         self.dropped_games = self.unrecorded_games = 0
+        self.flagged = False                 # some ply came with `full` flags: the packed batches carry the key
 
-    def append(self, ply, feat, policy, boards, hist, moved, keepalive=None):
+    def append(self, ply, feat, policy, boards, hist, moved, keepalive=None, full=None):
         """One ply of every slot: feat u64[G,144] (or its int64 bits), dense policy f32[G,1584], board records u8[G,64],
         history u32[G,2,4,2,6] (or its 384 bytes per slot), moved bool[G].  The arrays may be views into staging memory that
         `keepalive` owns and that is still being filled: nothing is read before settle / close_games / ply_record.
-        Entries older than the oldest running game are forgotten."""
-        self.entries.append({"ply": ply, "feat": np.asarray(feat).view(np.uint64), "policy": np.asarray(policy),
+        full (optional) u8[G]: 1 = this ply of that slot is a training row; the packed batches then carry the `full` key (a ply
+        logged without flags counts as all ones).  Entries older than the oldest running game are forgotten."""
+        if full is not None:
+            self.flagged = True
+        self.entries.append({"ply": ply, "full": None if full is None else np.asarray(full), "feat": np.asarray(feat).view(np.uint64), "policy": np.asarray(policy),
                              "boards": np.asarray(boards), "hist": np.asarray(hist).view(np.uint32).reshape(-1, 2, 4, 2, 6),
                              "moved": np.asarray(moved), "keepalive": keepalive})
         oldest = min(self.start_ply)
@@ -437,7 +480,7 @@ class PlyLog:
             return None
         self._entry_csr(e)
         del e["policy"]
-        for k in ("feat", "boards", "hist", "moved"):
+        for k in ("feat", "boards", "hist", "moved") + (("full",) if e.get("full") is not None else ()):
             e[k] = np.array(e[k])
         return e.pop("keepalive", None)
 
@@ -479,7 +522,7 @@ class PlyLog:
     def _pack(self, keep):
         S = np.asarray([k[0] for k in keep], dtype=np.int64)
         start = np.asarray([k[1] for k in keep], dtype=np.int64)
-        feat, hist, meta, cnt, pidx, pval, gk, ply = [], [], [], [], [], [], [], []
+        feat, hist, meta, cnt, pidx, pval, gk, ply, full = [], [], [], [], [], [], [], [], []
         for e in self.entries:
             k = np.flatnonzero(np.asarray(e["moved"])[S] & (e["ply"] >= start))
             if k.size == 0:
@@ -493,6 +536,8 @@ class PlyLog:
             feat.append(e["feat"][sl])
             hist.append(e["hist"][sl, persp])
             meta.append(np.stack([hlen, turn, persp], axis=1).astype(np.uint8))
+            if self.flagged:
+                full.append((e["full"][sl] != 0).astype(np.uint8) if e.get("full") is not None else np.ones(k.size, dtype=np.uint8))
             ptr, idx, val = self._entry_csr(e)
             c = ptr[sl + 1] - ptr[sl]
             src = np.repeat(ptr[sl] - (np.cumsum(c) - c), c) + np.arange(int(c.sum()))
@@ -514,7 +559,10 @@ class PlyLog:
         has = rows_per_game > 0                                 # a game without a logged row leaves no entry
         game_ptr = np.zeros(int(has.sum()) + 1, dtype=np.int64)
         np.cumsum(rows_per_game[has], out=game_ptr[1:])
-        return {"feat": np.concatenate(feat)[order], "hist": np.concatenate(hist)[order], "meta": np.concatenate(meta)[order],
-                "pol_idx": np.concatenate(pidx)[src], "pol_val": np.concatenate(pval)[src], "pol_ptr": new_ptr,
-                "game_ptr": game_ptr, "game_val": np.asarray([k[2] for k in keep], dtype=np.int8)[has],
-                "game_id": np.asarray([k[3] for k in keep], dtype=np.int64)[has]}
+        out = {"feat": np.concatenate(feat)[order], "hist": np.concatenate(hist)[order], "meta": np.concatenate(meta)[order],
+               "pol_idx": np.concatenate(pidx)[src], "pol_val": np.concatenate(pval)[src], "pol_ptr": new_ptr,
+               "game_ptr": game_ptr, "game_val": np.asarray([k[2] for k in keep], dtype=np.int8)[has],
+               "game_id": np.asarray([k[3] for k in keep], dtype=np.int64)[has]}
+        if self.flagged:
+            out[FULL_KEY] = np.concatenate(full)[order]
+        return out

@@ -96,6 +96,8 @@ def check_packed(packed):
     pol_ptr, game_ptr = np.asarray(packed["pol_ptr"]), np.asarray(packed["game_ptr"])
     if len(pol_ptr) != rows + 1 or len(game_ptr) != games + 1 or len(packed["feat"]) != rows or len(packed["hist"]) != rows:
         raise ValueError("packed batch: array lengths do not agree")
+    if records.FULL_KEY in packed and len(packed[records.FULL_KEY]) != rows:
+        raise ValueError("packed batch: the `full` flags do not cover the rows")
     if rows and (int(game_ptr[-1]) != rows or int(game_ptr[0]) != 0 or np.any(np.diff(game_ptr) < 0)):
         raise ValueError("packed batch: game_ptr does not partition the rows")
     width = np.diff(pol_ptr)
@@ -176,10 +178,19 @@ class ReplayBuffer:
     def add_packed(self, packed):
         """Append one packed batch (SelfPlay.drain_finished_packed, records.load_packed, SelfPlayWorker files): about
         1.5 KB per row go up, one launch files them.  A batch longer than the window keeps its last `capacity` rows; every
-        row's value is computed from its whole game.  -> rows in the batch."""
+        row's value is computed from its whole game.  -> rows in the batch.
+        With the optional `full` key (records.FULL_KEY) only the rows marked 1 enter the window, in order; the counters and
+        the return value count those rows, and each one's value still comes from all rows of its game."""
         import torch
         rows, games = check_packed(packed)
-        if rows == 0:
+        rank = None
+        if records.FULL_KEY in packed:
+            flags = np.asarray(packed[records.FULL_KEY]) != 0
+            kept = int(flags.sum())
+            rank = np.where(flags, np.cumsum(flags) - 1, -1).astype(np.int64)      # place among the kept rows, -1 = left out
+        else:
+            kept = rows
+        if kept == 0:
             self.games_seen += games
             return 0
         L, h = _lib.load(), self._handle()
@@ -190,10 +201,15 @@ class ReplayBuffer:
                  self._up(np.asarray(packed["game_ptr"], dtype=np.int64)), self._up(packed["game_val"])]
             if t[2].dtype != torch.uint8 or t[3].dtype != torch.int16 or t[4].dtype != torch.float32 or t[7].dtype != torch.int8:
                 raise ValueError("packed batch: meta u8, pol_idx i16, pol_val f32, game_val i8 expected")
-            _lib.check(L.hive_replay_append(h, *[_lib.ptr(x) for x in t], ctypes.c_void_p(pol_ptr.ctypes.data), rows, games, self._stream()))
-        self.rows_seen += rows
+            if rank is None:
+                _lib.check(L.hive_replay_append(h, *[_lib.ptr(x) for x in t], ctypes.c_void_p(pol_ptr.ctypes.data), rows, games,
+                                                self._stream()))
+            else:
+                _lib.check(L.hive_replay_append_ranked(h, *[_lib.ptr(x) for x in t], ctypes.c_void_p(pol_ptr.ctypes.data),
+                                                       _lib.ptr(self._up(rank)), rows, games, kept, self._stream()))
+        self.rows_seen += kept
         self.games_seen += games
-        return rows
+        return kept
 
     def add_file(self, path):
         return self.add_packed(records.load_packed(path))

@@ -142,6 +142,12 @@ def _game_worker(rank, world, cfg, out):
 
 
 class SelfPlayWorker:
+    """The multi-GPU self-play producer: one child process and one mcts.SelfPlay engine per GPU, the parent gathers their
+    packed batches and writes the files.
+
+    No playout_cap option here yet: every ply of every game gets `sims` simulations (mcts.SelfPlay(playout_cap=...) is the
+    single-engine route).  The hand-over formats do carry the optional `full` key of a packed batch when a batch has it."""
+
     def __init__(self, total_games, games_per_gpu=1024, sims=50, gpus=None, seed=0, net_seed=0, checkpoint=None, slots=1,
                  datapath="../dataSelf", games_per_file=100, report_every=10, worker=_game_worker, log=print, row_format="json",
                  net_dtype="auto", warmup=False, keep_results=True, spool=True):

@@ -220,6 +220,11 @@ int hive_leaf_store_stats(HiveLeafStore *s, uint64_t *served, uint64_t *inserted
  *           slot (head + i) mod capacity -- a batch longer than the ring keeps its last `capacity` rows -- with its policy
  *           in the fixed-width form and its value computed from its WHOLE game: the mover's side of game_val (0 = draw or
  *           length cap: -1 for both sides) times discount[later moves of the same side in that game].
+ *   append_ranked  append for a batch of which only some rows are training rows (the optional `full` key of a packed batch:
+ *           playout-cap self-play keeps its fast plies as rows of their games, marked): rank = DEVICE i64[rows], the row's
+ *           place among the kept rows (0 .. kept - 1 ascending, the exclusive running sum of the flags) or -1 = not kept.
+ *           Kept row i goes to slot (head + rank[i]) mod capacity, of more than `capacity` kept rows the last `capacity`
+ *           remain; live / appended count kept rows; every kept row's value still comes from ALL rows of its game.
  *   import  the same for rows in the form export returns (values and fixed-width policies as stored)
  *   export  the live rows, oldest first, into DEVICE arrays: feat u64[live][144], hist u32[live][48], meta u8[live][4]
  *           (the fourth byte is 0), pol_cnt i32[live], pol_idx i16[live][HIVE_LIST_CAP], pol_val f32[live][HIVE_LIST_CAP],
@@ -239,6 +244,10 @@ int hive_replay_stats(HiveReplay *r, int64_t *live, int64_t *appended, int64_t *
 int hive_replay_append(HiveReplay *r, const uint64_t *feat, const uint32_t *hist, const uint8_t *meta, const int16_t *pol_idx,
                        const float *pol_val, const int64_t *pol_ptr, const int64_t *game_ptr, const int8_t *game_val,
                        const int64_t *pol_ptr_host, int64_t rows, int64_t games, void *stream);
+int hive_replay_append_ranked(HiveReplay *r, const uint64_t *feat, const uint32_t *hist, const uint8_t *meta,
+                              const int16_t *pol_idx, const float *pol_val, const int64_t *pol_ptr, const int64_t *game_ptr,
+                              const int8_t *game_val, const int64_t *pol_ptr_host, const int64_t *rank, int64_t rows, int64_t games,
+                              int64_t kept, void *stream);
 int hive_replay_import(HiveReplay *r, const uint64_t *feat, const uint32_t *hist, const uint8_t *meta, const int32_t *pol_cnt,
                        const int16_t *pol_idx, const float *pol_val, const float *values, int64_t rows, void *stream);
 int hive_replay_export(HiveReplay *r, uint64_t *feat, uint32_t *hist, uint8_t *meta, int32_t *pol_cnt, int16_t *pol_idx,

@@ -156,6 +156,31 @@ int hive_search_root_stats(HiveSearch *s, float *visits, float *total_value, flo
  * in-flight slot had already created.  [0] unused. */
 int hive_search_leaf_histogram(HiveSearch *s, int32_t *hist);
 
+/* Per-game simulation budgets.  budget = DEVICE int32[games], quiet = DEVICE int8[games] (or NULL); the caller owns both and
+ * the handle keeps the pointers until the next call.  NULL, NULL (the default) switches the feature off.
+ * budget[g] = the simulations game g gets in each search: hive_search_select number `sim` of a search (0, 1, 2, ...: the
+ * count since hive_search_set_roots / hive_search_advance_roots, over all slots) treats a game with sim >= budget[g] exactly
+ * as an inactive one -- no leaf, no virtual loss, no histogram entry; hive_search_backup and hive_search_leaf_need then skip
+ * its row.  quiet[g] != 0 switches the root Dirichlet noise off for game g alone; the noise key of every other game is
+ * untouched.  Either search mode, any slots, with and without hive_search_advance_roots.
+ * The invariant: with the rounds of simulations laid out as TreeSearch lays them out (simulation 0 alone, then `slots` per
+ * round), a game with budget b <= sims ends a search of `sims` simulations with the tree a search of b simulations of the
+ * same batch gives it, bit for bit -- the noise is keyed on the simulation number, not on the batch.
+ * budget <= 0: the game gets no simulation; a fresh root then has no tree and hive_search_policy answers -2 for it (a tree
+ * kept by hive_search_advance_roots answers from the visits it carried). */
+int hive_search_set_budgets(HiveSearch *s, const int32_t *budget, const int8_t *quiet);
+
+/* Playout-cap randomisation: is this ply of game g searched in full or fast?  One thread per game; x = the first output of
+ * the search's counter-based generator keyed (seed ^ 0x8CB92BA72F3D8DD7, game_id[g], root turn, 0); the ply is full iff
+ * (x >> 32) < full_threshold, and always when full_threshold = 0xFFFFFFFF -- the host passes floor(p_full * 2^32), saturated.
+ * A pure function of (seed, game id, turn): not of the slot, batch size, process or GPU.  game_id = int64[n], root_boards =
+ * HiveBoard[n], active = int8[n] or NULL.  budget[g] (int32[n]) = full_sims or fast_sims, full[g] (int8[n], may be NULL) =
+ * 1 or 0, quiet[g] (int8[n], may be NULL: the caller does not want quiet fast plies) = !full[g]; a game with active == 0
+ * gets 0 in all three. */
+int hive_search_draw_budgets(uint64_t seed, const int64_t *game_id, const HiveBoard *root_boards, const int8_t *active, int n,
+                             int full_sims, int fast_sims, uint32_t full_threshold, int32_t *budget, int8_t *quiet, int8_t *full,
+                             void *stream);
+
 /* The search's own noise generator, exposed for statistical tests: draw d (= 0 .. draws-1) is what the root of game id
  * `first_game + d` would get at (turn, sim 0, slot 0): eta ~ Dirichlet(alpha) over k <= HIVE_EDGE_CAP edges
  * (solo_play.py:322-323, np.random.dirichlet).  out = float[draws][k]; prior = float[k] or NULL:
@@ -175,6 +200,11 @@ int hive_search_sample_noise(uint64_t seed, int64_t first_game, int turn, float 
  * device counters, the number of rows flagged is ADDED to them. */
 int hive_arena_split_launch(const HiveBoard *root_boards, const int8_t *a_white, const int8_t *need, int games, int slots,
                             int8_t *need_a, int8_t *need_b, uint64_t *rows_a, uint64_t *rows_b, void *stream);
+
+/* Unequal sides: budget[g] (int32[games], for hive_search_set_budgets) = sims_a when A owns the search of game g -- the
+ * ownership rule above -- else sims_b. */
+int hive_arena_budget_launch(const HiveBoard *root_boards, const int8_t *a_white, int games, int sims_a, int sims_b,
+                             int32_t *budget, void *stream);
 
 /* In place: the rows B owns take B's prediction, p_a[r][0..1583] = p_b[r][..] and v_a[r] = v_b[r]; A's own rows are
  * untouched.  p = float[slots * games][1584], 16-byte aligned; v = float[slots * games]. */

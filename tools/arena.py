@@ -5,7 +5,11 @@ ArenaResult and one JSON line.
 --bench: network A against a second InferenceNet built from the same weights, and, in the same process, a
 SelfPlay(keep_records=False) of the same games, simulations and noise setting; both games-per-minute figures and the rows
 each network evaluated go to profiles/arena_games_per_min.md.  The towers follow the rows they evaluate, the stem and the
-heads of both networks run over the full batch: the ratio to self-play is what the second network costs."""
+heads of both networks run over the full batch: the ratio to self-play is what the second network costs.
+
+--sims-b N: the sides search unequally, A with --sims and B with N simulations per move (Arena(sims_b=N)).  --same-weights
+builds B from A's weights: the match then measures what the extra simulations are worth with that network.  --append FILE
+adds the result as a section to a profile file."""
 import argparse
 import json
 import os
@@ -105,6 +109,9 @@ def main():
     ap.add_argument("--noise-eps", type=float, default=0.0)
     ap.add_argument("--min-score", type=float, default=0.55)
     ap.add_argument("--bench", action="store_true")
+    ap.add_argument("--sims-b", type=int, default=None, help="simulations per move of B (default: --sims, equal sides)")
+    ap.add_argument("--same-weights", action="store_true", help="B is a second InferenceNet of A's weights")
+    ap.add_argument("--append", default=None, metavar="FILE", help="append the result to this profile file")
     args = ap.parse_args()
     if len(args.checkpoints) not in (0, 2):
         ap.error("give two checkpoints, or none and --seed-a / --seed-b")
@@ -112,10 +119,10 @@ def main():
     net_a = load_net(ck[0], args.seed_a)
     if args.bench:
         return bench(args, net_a, DTYPES[args.dtype])
-    net_b = load_net(ck[1], args.seed_b)
+    net_b = net_a if args.same_weights else load_net(ck[1], args.seed_b)
     A, B = InferenceNet(net_a, dtype=DTYPES[args.dtype]), InferenceNet(net_b, dtype=DTYPES[args.dtype])
     ar = Arena(A, B, pairs=args.pairs, sims=args.sims, slots=args.slots, games_in_flight=args.games_in_flight, seed=args.seed,
-               opening_turns=args.opening_turns, noise_eps=args.noise_eps, keep_moves=False)
+               opening_turns=args.opening_turns, noise_eps=args.noise_eps, keep_moves=False, sims_b=args.sims_b)
     res, seconds = play(ar)
     rows = ar.rows_evaluated()
     assert ar.illegal_count() == 0
@@ -123,8 +130,20 @@ def main():
     print(res)
     d = res.as_dict()
     d.update(passes=res.passes(args.min_score), passes_ci=res.passes_ci(), seconds=seconds,
-             games_per_min=60.0 * res.games / seconds, rows_a=rows[0], rows_b=rows[1], sims=args.sims, seed=args.seed)
+             games_per_min=60.0 * res.games / seconds, rows_a=rows[0], rows_b=rows[1], sims=args.sims, seed=args.seed,
+             sims_b=args.sims_b if args.sims_b is not None else args.sims)
     print(json.dumps(d))
+    if args.append:
+        with open(args.append, "a") as f:
+            f.write(f"\n## Arena: {args.sims} against {d['sims_b']} simulations"
+                    + (", one set of weights" if args.same_weights else "") + "\n\n"
+                    f"`python tools/arena.py --pairs {args.pairs} --sims {args.sims} --sims-b {d['sims_b']} --seed {args.seed} "
+                    f"--noise-eps {args.noise_eps} --dtype {args.dtype}" + (" --same-weights" if args.same_weights else "") + "`\n\n"
+                    f"A searches {args.sims} simulations per move, B {d['sims_b']}.  {res!r}\n\n"
+                    f"Score of A {res.score:.3f}, 95 % interval [{res.score_ci95[0]:.3f}, {res.score_ci95[1]:.3f}] over "
+                    f"{len(res.pair_scores)} pairs ({res.games} games in {seconds:.1f} s); rows through a tower: A {rows[0]}, "
+                    f"B {rows[1]}.\n")
+        print("appended to", args.append)
 
 
 if __name__ == "__main__":

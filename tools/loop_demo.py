@@ -10,7 +10,11 @@ the network the round started from, and the self-play evaluator is refreshed onl
 
 --replay ROWS (default 0 = train on the round's own rows, as above): the rounds share one replay.ReplayBuffer of ROWS rows
 on the GPU; every round appends its packed batches (1.5 KB per row go up, nothing is widened ahead of time) and the 20
-training steps draw their minibatches from the whole window with buf.sample(512, step=...) -- one launch per minibatch."""
+training steps draw their minibatches from the whole window with buf.sample(512, step=...) -- one launch per minibatch.
+
+--playout-cap FULL,FAST,P (default off): playout-cap randomisation, mcts.SelfPlay(playout_cap=...): a ply is searched with
+FULL simulations with probability P and becomes a training row, else with FAST simulations and no root noise; the round's
+search then runs max(FULL, FAST) simulations and the trainer sees the rows flagged full (both routes filter them)."""
 import argparse, os, sys, time, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hive_alphazero_amd import mcts, records
@@ -19,13 +23,18 @@ from hive_alphazero_amd.alpha_net import ChessNet, InferenceNet, Trainer
 ap = argparse.ArgumentParser()
 ap.add_argument("--gate", type=int, default=0, metavar="PAIRS", help="arena pairs that gate the refresh (0 = refresh always)")
 ap.add_argument("--replay", type=int, default=0, metavar="ROWS", help="train from a replay window of ROWS rows shared by the rounds (0 = off)")
+ap.add_argument("--playout-cap", default=None, metavar="FULL,FAST,P", help="full / fast simulations and the share of full plies, e.g. 16,4,0.25")
 opts = ap.parse_args()
 gate, window = opts.gate, opts.replay
+cap = None
+if opts.playout_cap:
+    full, fast, p_full = opts.playout_cap.split(",")
+    cap = {"full": int(full), "fast": int(fast), "p_full": float(p_full)}
 buf = None
 if window > 0:
     from hive_alphazero_amd.replay import ReplayBuffer
     buf = ReplayBuffer(window)
-games, sims, rounds = 256, 16, 2
+games, sims, rounds = 256, (max(cap["full"], cap["fast"]) if cap else 16), 2
 torch.manual_seed(0)
 net = ChessNet().cuda()
 evaluator = InferenceNet(net)
@@ -33,7 +42,7 @@ trainer = Trainer(net)
 for rnd in range(rounds):
     net.eval()
     sp = mcts.SelfPlay(games, sims, evaluator, seed=100 + rnd, game_ids=range(rnd * games, (rnd + 1) * games),
-                       packed_records=True, max_finished_kept=2 * games)
+                       packed_records=True, max_finished_kept=2 * games, playout_cap=cap)
     t0 = time.perf_counter()
     batches = []
     while sp.running() and sp.plies < 80:
@@ -49,9 +58,7 @@ for rnd in range(rounds):
     packed = records.concat_packed(batches)
     t0 = time.perf_counter()
     if buf is not None:
-        for b in batches:
-            buf.add_packed(b)
-        n = len(packed["meta"])
+        n = sum(buf.add_packed(b) for b in batches)
     else:
         states, policies, values = records.dataset_tensors_gpu_packed(packed, dtype=torch.float32, layout="chw")
         n = states.shape[0]
@@ -85,6 +92,7 @@ for rnd in range(rounds):
           + (f"{n} rows of {records.packed_games(packed)} games widened on the GPU in {t_ds * 1e3:.0f} ms; " if buf is None else
              f"{n} rows of {records.packed_games(packed)} games appended to the replay window in {t_ds * 1e3:.0f} ms "
              f"(fill {len(buf)} / {buf.capacity} rows, {buf.rows_seen} seen); ") +
+          (f"{len(packed['meta'])} plies, {n} of them full; " if cap else "") +
           f"20 training steps of 512 in {t_tr:.1f} s, loss {losses[0]:.3f} -> {losses[-1]:.3f}", flush=True)
     assert illegal == 0 and all(np.isfinite(l) for l in losses) and records.packed_games(packed) == games
 print("ok")
