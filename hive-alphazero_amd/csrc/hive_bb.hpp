@@ -18,6 +18,18 @@
 //   d0 = (0,+1) R   d1 = (+1,+1) UR   d2 = (+1,0) U   d3 = (0,-1) L   d4 = (-1,-1) DL   d5 = (-1,0) D
 // consecutive directions are mutually adjacent, so the two cells flanking a step along
 // d_i are c + d_(i-1) and c + d_(i+1) (reference move_checker.py:193-198 "overlap_tiles").
+//
+// The slide step, two ways.  cs_i bit c = exactly one flank of the step c -> c + d_i is occupied; `allowed` = empty cells
+// touching the hive.  Push form (slide_step: gate the sources, shift, gate the destinations), four row shifts:
+//   allowed & ( up(x & cs2) | down(x & cs5) | right((x & cs0) | up(x & cs1)) | left((x & cs3) | down(x & cs4)) )
+// The shifts are bijections of the torus, so they distribute over AND and OR, and right/left are inverse to each other:
+// allowed & right(y) = right(left(allowed) & y), up(x & cs) = up(x) & up(cs).  Every gate board can therefore be moved
+// behind the row shift and `allowed` folded into it, once per (board, piece).  Pull form (pull_step), two row shifts:
+//   P0 = cs0 & left(allowed)    P1 = up(cs1)   & left(allowed)    P2 = up(cs2)   & allowed
+//   P3 = cs3 & right(allowed)   P4 = down(cs4) & right(allowed)   P5 = down(cs5) & allowed
+//   u = up(x), d = down(x):  (u & P2) | (d & P5) | right((x & P0) | (u & P1)) | left((x & P3) | (d & P4))
+// A slide edge and its reverse have the same two flanks, hence up(cs2) = cs5 and down(cs5) = cs2; with S_i bit c =
+// occ[c + d_i], cs1 = S0 ^ S2 and S2 = down(occ) give up(cs1) = up(S0) ^ occ, likewise down(cs4) = down(S3) ^ occ.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -241,6 +253,41 @@ __device__ __forceinline__ B slide_raw(const SlideCtxT<B> &c, B x)
 }
 template <class B>
 __device__ __forceinline__ B slide_step(const SlideCtxT<B> &c, B x) { return bb_and(slide_raw(c, x), c.allowed); }
+
+// The same step in pull form, for the pieces that take many steps on one board (Ant flood, Spider walk): see the header
+// comment.  P[i] bit c: a piece standing on c (P0, P3), on c + D (P1, P2) or on c + U (P4, P5) after the row shift may
+// take step d_i, and the cell it reaches is allowed.
+template <class B>
+struct PullCtxT {
+    B P[6];
+};
+
+// Built straight from the occupancy views (no SlideCtxT in between: the Ant and Spider branches of piece_dests have no
+// registers to spare for one).  Uses  up(cs2) == cs5,  down(cs5) == cs2,  up(cs1) == up(S0) ^ occ,  down(cs4) == down(S3) ^ occ.
+template <class B>
+__device__ __forceinline__ PullCtxT<B> make_pull_ctx(B occ, const B S[6])
+{
+    PullCtxT<B> p;
+    const B allowed = bb_andn(bb_or(bb_or3(S[0], S[1], S[2]), bb_or3(S[3], S[4], S[5])), occ);
+    const B al = bb_left(allowed), ar = bb_right(allowed);
+    p.P[2] = bb_and(bb_xor(S[4], S[0]), allowed);                     // up(cs2) = cs5
+    p.P[5] = bb_and(bb_xor(S[1], S[3]), allowed);                     // down(cs5) = cs2
+    p.P[0] = bb_and(bb_xor(S[5], S[1]), al);                          // cs0
+    p.P[3] = bb_and(bb_xor(S[2], S[4]), ar);                          // cs3
+    p.P[1] = bb_and(bb_xor(bb_left(S[5]), occ), al);                  // up(cs1): up(S0) = left(up(occ)) = left(S5)
+    p.P[4] = bb_and(bb_xor(bb_right(S[2]), occ), ar);                 // down(cs4): down(S3) = right(down(occ)) = right(S2)
+    return p;
+}
+
+// == slide_step(make_slide_ctx(occ, S), x), bit for bit
+template <class B>
+__device__ __forceinline__ B pull_step(const PullCtxT<B> &p, B x)
+{
+    const B u = bb_up(x), d = bb_down(x);
+    const B r = bb_right(bb_or(bb_and(x, p.P[0]), bb_and(u, p.P[1])));
+    const B l = bb_left(bb_or(bb_and(x, p.P[3]), bb_and(d, p.P[4])));
+    return bb_or(bb_or3(bb_and(u, p.P[2]), bb_and(d, p.P[5]), r), l);
+}
 
 // lowest set cell of a board (row-major order), as a single-cell board; empty -> empty
 __device__ __forceinline__ BB bb_lowest(BB x)

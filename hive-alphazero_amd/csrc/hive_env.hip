@@ -63,6 +63,11 @@ constexpr int NW = 11;                 // waves per workgroup = piece slots per 
 #ifndef HIVE_PAIR_ANT_STEPS
 #define HIVE_PAIR_ANT_STEPS HIVE_ANT_STEPS
 #endif
+#ifndef HIVE_MASK_STORE
+#define HIVE_MASK_STORE 0               // the quad path's 8-byte mask stores: 0 plain, 1 nontemporal, 2 agent-scope relaxed atomic (write-
+                                        // through: -1.6 % on a lone launch of up to 16 K boards, +4.4 % at 1 M boards, twice the bytes
+                                        // written -- profiles/r05_movegen_pull_step.md)
+#endif
 #ifndef HIVE_PAIR_WPE
 #define HIVE_PAIR_WPE 6                 // ... of the pair-layout variant (three registers per board value instead of two)
 #endif
@@ -228,10 +233,11 @@ __device__ __forceinline__ PieceInfoT<typename L::B> piece_dests(const PieceArgs
     } else {
         BB S[6];
         occupancy_views(occp, S);
-        SlideCtxT<BB> ctx = make_slide_ctx(occp, S);
-        if (type == T_QUEEN) {
-            rule = slide_step(ctx, srcbit);                       // pieces.py:35-44
-        } else if (type == T_ANT) {
+        // The Ant and the Spider take many slide steps on this board: they use the pull form (hive_bb.hpp), whose six gate
+        // boards are all that stays alive across their loops.  Queen and Beetle take one step, which does not pay for that
+        // set-up.
+        if (type == T_ANT) {
+            const PullCtxT<BB> pull = make_pull_ctx(occp, S);
             BB R = srcbit;                                        // pieces.py:59-63, move_checker.py:217-246
             bool aa = on_top;
             while (__any(aa)) {
@@ -240,45 +246,50 @@ __device__ __forceinline__ PieceInfoT<typename L::B> piece_dests(const PieceArgs
                     BB nx = R, before_last = R;
                     HIVE_UNROLL for (int u = 0; u < ANT_STEPS; ++u) {
                         before_last = nx;
-                        nx = bb_or(nx, slide_step(ctx, nx));
+                        nx = bb_or(nx, pull_step(pull, nx));
                     }
                     if (bb_eq(nx, before_last)) aa = false;     // the last expansion added nothing: closed
                     R = nx;
                 }
             }
             rule = bb_andn(R, srcbit);
-        } else {
-            // both flanks occupied (k == 2) per direction
-            BB b0 = bb_and(S[5], S[1]), b1 = bb_and(S[0], S[2]), b2 = bb_and(S[1], S[3]);
-            BB b3 = bb_and(S[2], S[4]), b4 = bb_and(S[3], S[5]), b5 = bb_and(S[4], S[0]);
-            if (type == T_SPIDER) {
-                // pieces.py:78-85: simple path of exactly three k==1 steps, then the direct-hop veto.
-                // For each first step a: {c} = slide(slide(a) \ src) \ {src, a}; c != b holds by itself.
-                BB A = slide_step(ctx, srcbit);
-                BB acc = L::zero();
-                bool sa = on_top && bb_any(A);
-                while (__any(sa)) {
-                    HIVE_COUNT_ITER();
-                    if (sa) {
-                        BB a = bb_lowest(A);
-                        A = bb_andn(A, a);
-                        BB Bs = bb_andn(slide_step(ctx, a), srcbit);
-                        BB Cs = bb_andn(bb_andn(slide_step(ctx, Bs), srcbit), a);
-                        acc = bb_or(acc, Cs);
-                        sa = bb_any(A);
-                    }
+        } else if (type == T_SPIDER) {
+            // pieces.py:78-85: simple path of exactly three k==1 steps, then the direct-hop veto: a direct step from src
+            // with both flanks occupied (k == 2).  The veto needs only srcbit and the views, so it is formed ahead of the loop.
+            const BB veto = shift_dirs(bb_and(srcbit, bb_and(S[5], S[1])), bb_and(srcbit, bb_and(S[0], S[2])),
+                                       bb_and(srcbit, bb_and(S[1], S[3])), bb_and(srcbit, bb_and(S[2], S[4])),
+                                       bb_and(srcbit, bb_and(S[3], S[5])), bb_and(srcbit, bb_and(S[4], S[0])));
+            const PullCtxT<BB> pull = make_pull_ctx(occp, S);
+            // For each first step a: {c} = slide(slide(a) \ src) \ {src, a}; c != b holds by itself.
+            BB A = pull_step(pull, srcbit);
+            BB acc = L::zero();
+            bool sa = on_top && bb_any(A);
+            while (__any(sa)) {
+                HIVE_COUNT_ITER();
+                if (sa) {
+                    BB a = bb_lowest(A);
+                    A = bb_andn(A, a);
+                    BB Bs = bb_andn(pull_step(pull, a), srcbit);
+                    BB Cs = bb_andn(bb_andn(pull_step(pull, Bs), srcbit), a);
+                    acc = bb_or(acc, Cs);
+                    sa = bb_any(A);
                 }
-                BB veto = shift_dirs(bb_and(srcbit, b0), bb_and(srcbit, b1), bb_and(srcbit, b2),
-                                     bb_and(srcbit, b3), bb_and(srcbit, b4), bb_and(srcbit, b5));
-                rule = bb_andn(acc, veto);
+            }
+            rule = bb_andn(acc, veto);
+        } else {
+            const SlideCtxT<BB> ctx = make_slide_ctx(occp, S);
+            if (type == T_QUEEN) {
+                rule = slide_step(ctx, srcbit);                       // pieces.py:35-44
             } else {
-                // Beetle, pieces.py:100-113 + move_checker.py:201-209
-                BB Q1 = slide_raw(ctx, srcbit);
-                BB Q0 = shift_dirs(bb_andn(bb_andn(srcbit, ctx.cs[0]), b0), bb_andn(bb_andn(srcbit, ctx.cs[1]), b1),
-                                   bb_andn(bb_andn(srcbit, ctx.cs[2]), b2), bb_andn(bb_andn(srcbit, ctx.cs[3]), b3),
-                                   bb_andn(bb_andn(srcbit, ctx.cs[4]), b4), bb_andn(bb_andn(srcbit, ctx.cs[5]), b5));
+                // Beetle, pieces.py:100-113 + move_checker.py:201-209: a step with one flank occupied (k == 1) goes anywhere,
+                // one with none (k == 0) only to a cell touching the hive, one with both (k == 2) nowhere.  A k == 1 step ends
+                // next to its occupied flank, so it touches the hive as well: both cases are "not k == 2, and touching".
+                BB b0 = bb_and(S[5], S[1]), b1 = bb_and(S[0], S[2]), b2 = bb_and(S[1], S[3]);
+                BB b3 = bb_and(S[2], S[4]), b4 = bb_and(S[3], S[5]), b5 = bb_and(S[4], S[0]);
+                BB Q = shift_dirs(bb_andn(srcbit, b0), bb_andn(srcbit, b1), bb_andn(srcbit, b2),
+                                  bb_andn(srcbit, b3), bb_andn(srcbit, b4), bb_andn(srcbit, b5));
                 const BB nb = kLate ? load_nsrc() : nsrc;
-                rule = bb_or3(bb_and(nb, occ), Q1, bb_and(Q0, ctx.nocc));
+                rule = bb_or(bb_and(nb, occ), bb_and(Q, ctx.nocc));
                 if (stacked) rule = bb_or(rule, nb);
             }
         }
@@ -702,9 +713,18 @@ hive_piece_kernel(const HiveBoard *__restrict__ boards, int n, uint32_t *__restr
     if (own && (mask != nullptr || count != nullptr)) {
         // the legal set leaves as it is: slot wv's destination board, two words per lane, straight to HBM
         if constexpr (L::kLanes == 4) {
-        if (valid && mask != nullptr && (lane & 3) < 3)
-            *reinterpret_cast<uint2 *>(mask + (gbase + bl) * HIVE_MASK_WORDS + wv * 6 + 2 * (lane & 3)) =
-                make_uint2(pc.D.lo, pc.D.hi);
+        if (valid && mask != nullptr && (lane & 3) < 3) {
+            uint32_t *mp = mask + (gbase + bl) * HIVE_MASK_WORDS + wv * 6 + 2 * (lane & 3);
+#if HIVE_MASK_STORE == 1
+            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+            __builtin_nontemporal_store(u32x2{pc.D.lo, pc.D.hi}, reinterpret_cast<u32x2 *>(mp));
+#elif HIVE_MASK_STORE == 2
+            __hip_atomic_store(reinterpret_cast<unsigned long long *>(mp), (unsigned long long)pc.D.lo | ((unsigned long long)pc.D.hi << 32),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+            *reinterpret_cast<uint2 *>(mp) = make_uint2(pc.D.lo, pc.D.hi);
+#endif
+        }
         } else {
             int b3 = (int)(threadIdx.x & 63u) >> L::kShift;      // (built again, like late_args above)
             asm volatile("" : "+v"(b3));
@@ -999,6 +1019,28 @@ __global__ void hive_tables_kernel(uint32_t *line, uint8_t *nbr)
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < kCells * 6) line[i] = (&d_tables.line[0][0])[i];
     if (i < kCells * 8) nbr[i] = (&d_tables.nbr[0][0])[i];
+}
+
+// debug/test hook: one slide step per board in the push and in the pull form (tests/test_slide_step.py).  Every lane of a
+// wave runs the shifts (they read neighbour lanes); boards past n are empty and are not stored.
+template <class L>
+__global__ void __launch_bounds__(256)
+hive_slide_step_kernel(const uint32_t *__restrict__ occ, const uint32_t *__restrict__ src, int n,
+                       uint32_t *__restrict__ push, uint32_t *__restrict__ pull)
+{
+    using B = typename L::B;
+    const long long item = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> L::kShift;
+    const bool valid = item < n;
+    const B o = valid ? L::load(occ + item * 6) : L::zero();
+    const B x = valid ? L::load(src + item * 6) : L::zero();
+    B S[6];
+    occupancy_views(o, S);
+    const B a = slide_step(make_slide_ctx(o, S), x);
+    const B b = pull_step(make_pull_ctx(o, S), x);
+    if (valid) {
+        L::store(push + item * 6, a);
+        L::store(pull + item * 6, b);
+    }
 }
 
 
@@ -1600,6 +1642,22 @@ int hive_debug_stamps(unsigned long long *host88)
 int hive_debug_tables(uint32_t *line /* [144*6] */, uint8_t *nbr /* [144*8] */, void *stream)
 {
     hipLaunchKernelGGL(hive_tables_kernel, dim3(5), dim3(256), 0, (hipStream_t)stream, line, nbr);
+    HIP_TRY(hipGetLastError());
+    return HIVE_OK;
+}
+
+// test hook: slide_step against pull_step (hive_bb.hpp), one step per board, in either lane layout
+int hive_debug_slide_step(const uint32_t *occ, const uint32_t *src, int n, int pair_layout, uint32_t *push_out,
+                          uint32_t *pull_out, void *stream)
+{
+    if (!occ || !src || !push_out || !pull_out || n <= 0) return fail(HIVE_E_ARG, "hive_debug_slide_step: null argument or n <= 0");
+    if (pair_layout) {
+        const unsigned blocks = (unsigned)(((long long)n * 2 + 255) / 256);
+        hipLaunchKernelGGL(hive_slide_step_kernel<PairLay>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, occ, src, n, push_out, pull_out);
+    } else {
+        const unsigned blocks = (unsigned)(((long long)n * 4 + 255) / 256);
+        hipLaunchKernelGGL(hive_slide_step_kernel<QuadLay>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, occ, src, n, push_out, pull_out);
+    }
     HIP_TRY(hipGetLastError());
     return HIVE_OK;
 }

@@ -145,6 +145,12 @@ int hive_movegen_launch(const HiveBoard *boards, int n, uint32_t *mask, int32_t 
  * threshold (INT_MAX: never), 0 restores the default (16384), < 0 only asks; returns the previous value.  Process-wide;
  * meant for tests and measurements, not for the hot path. */
 int hive_movegen_pair_threshold(int boards);
+/* Test hook: one slide step (move_checker.py:189-214, the k == 1 gate rule) of every cell of src[i] on the board occ[i],
+ * computed twice: by the push form the Queen and the Beetle use and by the pull form of the Ant flood and the Spider walk.
+ * occ, src, push_out, pull_out = device uint32[n][6] (word r = rows 2r, 2r+1; column c = bit c of the 16-bit field);
+ * pair_layout != 0 runs the two-lanes-per-board code, else the quad code.  One kernel launch; nothing else is touched. */
+int hive_debug_slide_step(const uint32_t *occ, const uint32_t *src, int n, int pair_layout, uint32_t *push_out,
+                          uint32_t *pull_out, void *stream);
 /* workspace = device scratch of n * HIVE_CELLS * 8 bytes (the packed 56-bit-per-cell features). */
 int hive_encode_launch(const HiveBoard *boards, const HiveHistory *hist, int n, void *planes,
                        HiveDType dtype, HiveLayout layout, void *workspace, void *stream);
