@@ -48,6 +48,8 @@ struct SearchDev {
     int sims_room;                                 // nodes a carried tree must leave free (hive_search_set_carry_room)
     const int32_t *budget;                         // [G] simulations of this search per game, or nullptr (hive_search_set_budgets)
     const int8_t *quiet;                           // [G] != 0: no root noise for that game, or nullptr
+    int32_t *clock;                                // [G] simulations of its own search each game has run, or nullptr: one
+                                                   // host counter for the whole batch (hive_search_set_rolling)
 };
 
 // the node arrays of one pool: hive_search_advance_roots moves the kept subtrees from the handle's pool into a second one
@@ -183,12 +185,13 @@ __device__ __forceinline__ void tt_insert(const SearchDev &S, int g, const uint3
 
 // ------------------------------------------------------------------ kernels
 __global__ void __launch_bounds__(256)
-search_reset_kernel(SearchDev S, const HiveBoard *__restrict__ boards, const HiveHistory *__restrict__ hist,
-                    const int8_t *__restrict__ active)
+search_reset_kernel(SearchDev S, const int8_t *__restrict__ which, const HiveBoard *__restrict__ boards,
+                    const HiveHistory *__restrict__ hist, const int8_t *__restrict__ active)
 {
     const int lane = threadIdx.x & 63;
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (g >= S.G) return;
+    if (which != nullptr && which[g] == 0) return;          // hive_search_restart: every other game keeps every byte
     wave_copy(&S.root_board[g], &boards[g], sizeof(HiveBoard), lane);
     wave_copy(&S.root_hist[g], &hist[g], sizeof(HiveHistory), lane);
     for (int i = lane; i < S.TT; i += 64) S.tt[(long long)g * S.TT + i] = -1;
@@ -196,6 +199,7 @@ search_reset_kernel(SearchDev S, const HiveBoard *__restrict__ boards, const Hiv
         S.n_nodes[g] = 0;
         S.root_pending[g] = 0;
         S.active[g] = active ? active[g] : 1;
+        if (S.clock != nullptr) S.clock[g] = 0;
     }
 }
 
@@ -211,7 +215,15 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
     const long long sg = (long long)slot * S.G + g;
     int32_t *pnode = S.path_node + sg * S.MN, *pedge = S.path_edge + sg * S.MN;
     // a game whose budget is spent sits the rest of the search out exactly like an inactive one: no leaf, no virtual loss
-    const bool spent = S.budget != nullptr && (long long)sim >= (long long)S.budget[g];
+    bool spent;
+    if (S.clock != nullptr) {
+        // rolling: the game's own clock numbers its simulations -- 0 alone, then `slots` per round (TreeSearch's layout)
+        const int c = S.clock[g];
+        spent = !(c + slot < S.budget[g] && (c > 0 || slot == 0));
+        sim = (unsigned long long)(c + slot);
+    } else {
+        spent = S.budget != nullptr && (long long)sim >= (long long)S.budget[g];
+    }
     if (!S.active[g] || spent) { if (lane == 0) { S.leaf_kind[sg] = LEAF_NONE; S.path_len[sg] = 0; } return; }
 
     if (S.n_nodes[g] == 0) {
@@ -465,7 +477,7 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
 
 // solo_play.py:337-374 + self_play.py:139-157
 __global__ void __launch_bounds__(256)
-search_policy_kernel(SearchDev S, float *__restrict__ policy, int32_t *__restrict__ action,
+search_policy_kernel(SearchDev S, const int8_t *__restrict__ which, float *__restrict__ policy, int32_t *__restrict__ action,
                      int32_t *__restrict__ sum_n_out, int selfplay)
 {
     const int lane = threadIdx.x & 63;
@@ -473,7 +485,8 @@ search_policy_kernel(SearchDev S, float *__restrict__ policy, int32_t *__restric
     if (g >= S.G) return;
     float *pol = policy ? policy + (long long)g * HIVE_ACTIONS : nullptr;
     if (pol) for (int i = lane; i < HIVE_ACTIONS; i += 64) pol[i] = 0.f;
-    if (!S.active[g] || S.n_nodes[g] == 0 || S.node_term[(long long)g * S.MN]) {
+    // hive_search_policy_where: a game outside `which` is answered as an inactive one
+    if ((which != nullptr && which[g] == 0) || !S.active[g] || S.n_nodes[g] == 0 || S.node_term[(long long)g * S.MN]) {
         if (lane == 0) { action[g] = -2; if (sum_n_out) sum_n_out[g] = 0; }
         return;
     }
@@ -638,6 +651,23 @@ search_draw_budgets_kernel(unsigned long long seed, const long long *__restrict_
     if (full) full[g] = f ? 1 : 0;
 }
 
+// hive_search_round_end: one thread per game, after the backups of a rolling round
+__global__ void __launch_bounds__(256)
+search_round_end_kernel(SearchDev S, int slots_run, int8_t *__restrict__ done)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= S.G) return;
+    const bool on = S.active[g] != 0;
+    const int b = S.budget[g];
+    int c = S.clock[g];
+    if (on && c < b) {
+        const int left = b - c;
+        c += c == 0 ? 1 : (slots_run < left ? slots_run : left);      // the root-opening simulation runs alone
+        S.clock[g] = c;
+    }
+    done[g] = (on && c >= b) ? 1 : 0;
+}
+
 // lanes of one wave see each other's LDS / global writes made before this point
 __device__ __forceinline__ void wave_sync()
 {
@@ -799,6 +829,7 @@ struct HiveSearch {
     int npool = 0;
     NodePool alt{};             // second node pool of hive_search_advance_roots, allocated on first use
     bool have_alt = false;
+    int32_t *clock_mem = nullptr;   // hive_search_set_rolling: the per-game clocks, allocated on first use
 };
 
 template <typename T>
@@ -929,9 +960,56 @@ int hive_search_set_roots(HiveSearch *s, const HiveBoard *boards, const HiveHist
 {
     if (!s || !boards || !hist) return hive::set_error(HIVE_E_ARG, "null argument");
     S_TRY(hipSetDevice(s->device));
-    hipLaunchKernelGGL(search_reset_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, boards, hist, active);
+    hipLaunchKernelGGL(search_reset_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, (const int8_t *)nullptr, boards,
+                       hist, active);
     S_TRY(hipGetLastError());
     s->sim = 0;                 // simulations are numbered inside one search: part of the noise key (hive_search_set_game_ids)
+    return HIVE_OK;
+}
+
+int hive_search_set_rolling(HiveSearch *s, int on)
+{
+    if (!s) return hive::set_error(HIVE_E_ARG, "null handle");
+    S_TRY(hipSetDevice(s->device));
+    if (!on) {
+        s->d.clock = nullptr;
+        return HIVE_OK;
+    }
+    if (s->clock_mem == nullptr) S_TRY(alloc(s, &s->clock_mem, (size_t)s->d.G));
+    S_TRY(hipMemsetAsync(s->clock_mem, 0, sizeof(int32_t) * (size_t)s->d.G, s->stream));
+    s->d.clock = s->clock_mem;
+    return HIVE_OK;
+}
+
+int hive_search_restart(HiveSearch *s, const int8_t *which, const HiveBoard *boards, const HiveHistory *hist,
+                        const int8_t *active)
+{
+    if (!s || !which || !boards || !hist) return hive::set_error(HIVE_E_ARG, "null argument");
+    if (!s->d.clock) return hive::set_error(HIVE_E_ARG, "hive_search_restart: the handle is not rolling (hive_search_set_rolling)");
+    S_TRY(hipSetDevice(s->device));
+    hipLaunchKernelGGL(search_reset_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, which, boards, hist, active);
+    S_TRY(hipGetLastError());
+    return HIVE_OK;
+}
+
+int hive_search_round_end(HiveSearch *s, int slots_run, int8_t *done)
+{
+    if (!s || !done || slots_run < 1 || slots_run > s->d.L) return hive::set_error(HIVE_E_ARG, "hive_search_round_end: bad argument");
+    if (!s->d.clock || !s->d.budget)
+        return hive::set_error(HIVE_E_ARG, "hive_search_round_end: needs hive_search_set_rolling and hive_search_set_budgets");
+    S_TRY(hipSetDevice(s->device));
+    hipLaunchKernelGGL(search_round_end_kernel, dim3((unsigned)((s->d.G + 255) / 256)), dim3(256), 0, s->stream, s->d, slots_run,
+                       done);
+    S_TRY(hipGetLastError());
+    return HIVE_OK;
+}
+
+int hive_search_clocks(HiveSearch *s, int32_t *clock)
+{
+    if (!s || !clock) return hive::set_error(HIVE_E_ARG, "null argument");
+    if (!s->d.clock) return hive::set_error(HIVE_E_ARG, "hive_search_clocks: the handle is not rolling (hive_search_set_rolling)");
+    S_TRY(hipSetDevice(s->device));
+    S_TRY(hipMemcpyAsync(clock, s->d.clock, sizeof(int32_t) * (size_t)s->d.G, hipMemcpyDeviceToDevice, s->stream));
     return HIVE_OK;
 }
 
@@ -968,6 +1046,8 @@ int hive_search_advance_roots(HiveSearch *s, const int32_t *played, const HiveBo
                               const int8_t *active)
 {
     if (!s || !boards || !hist) return hive::set_error(HIVE_E_ARG, "null argument");
+    if (s->d.clock)
+        return hive::set_error(HIVE_E_ARG, "hive_search_advance_roots: not with per-game clocks (hive_search_set_rolling)");
     S_TRY(hipSetDevice(s->device));
     SearchDev &d = s->d;
     // LDS per game: map + queue, 8 bytes per node; four games per workgroup while that fits into 64 KB, else one
@@ -1047,6 +1127,8 @@ int hive_search_export_tree(HiveSearch *s, int game, int32_t *n_nodes, HiveBoard
 int hive_search_select(HiveSearch *s, int slot, HiveBoard *leaf_boards, HiveHistory *leaf_hist)
 {
     if (!s || !leaf_boards || !leaf_hist || slot < 0 || slot >= s->d.L) return hive::set_error(HIVE_E_ARG, "bad argument");
+    if (s->d.clock && !s->d.budget)
+        return hive::set_error(HIVE_E_ARG, "hive_search_select: per-game clocks need budgets (hive_search_set_budgets)");
     S_TRY(hipSetDevice(s->device));
     hipLaunchKernelGGL(search_select_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, slot, s->sim++, leaf_boards,
                        leaf_hist);
@@ -1082,7 +1164,18 @@ int hive_search_policy(HiveSearch *s, float *policy, int32_t *action, int32_t *s
 {
     if (!s || !action) return hive::set_error(HIVE_E_ARG, "null argument");
     S_TRY(hipSetDevice(s->device));
-    hipLaunchKernelGGL(search_policy_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, policy, action, sum_n, selfplay);
+    hipLaunchKernelGGL(search_policy_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, (const int8_t *)nullptr, policy,
+                       action, sum_n, selfplay);
+    S_TRY(hipGetLastError());
+    return HIVE_OK;
+}
+
+int hive_search_policy_where(HiveSearch *s, const int8_t *which, float *policy, int32_t *action, int32_t *sum_n, int selfplay)
+{
+    if (!s || !which || !action) return hive::set_error(HIVE_E_ARG, "null argument");
+    S_TRY(hipSetDevice(s->device));
+    hipLaunchKernelGGL(search_policy_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, which, policy, action, sum_n,
+                       selfplay);
     S_TRY(hipGetLastError());
     return HIVE_OK;
 }

@@ -48,6 +48,29 @@ def playout_cap_draw(seed, game_ids, turns, p_full):
     return (x >> np.uint64(32)) < np.uint64(thr)
 
 
+def rolling_clock_step(clock, budget, active, slots):
+    """One round of a rolling search in numpy (no GPU): the rule of search_select_kernel's per-game clocks and of
+    hive_search_round_end.  clock / budget int[n], active bool-like[n] -> (takes_part bool[n, slots], clock after the round
+    int64[n], done bool[n]).  An active game at clock c with budget b runs slot sl iff c + sl < b and (c > 0 or sl == 0) -- the
+    root-opening simulation runs alone -- as simulation number c + sl; the round moves its clock by 1 from 0, else by
+    min(slots, b - c); done = active and clock >= budget.  Iterated from 0 this lays a game's simulations out as
+    TreeSearch.run_simulations does for sims = b: 0 alone, then `slots` per round."""
+    import numpy as np
+    c = np.asarray(clock, dtype=np.int64)
+    b = np.asarray(budget, dtype=np.int64)
+    on = np.asarray(active) != 0
+    sl = np.arange(int(slots), dtype=np.int64)[None, :]
+    part = on[:, None] & (c[:, None] + sl < b[:, None]) & ((c[:, None] > 0) | (sl == 0))
+    step = np.where(c == 0, 1, np.minimum(int(slots), b - c))
+    after = np.where(on & (c < b), c + step, c)
+    return part, after, on & (after >= b)
+
+
+def rolling_quantum(sims, slots):
+    """Rounds a rolling search of `sims` simulations takes: the opening one alone, then `slots` per round."""
+    return 1 + -(-(int(sims) - 1) // int(slots))
+
+
 class _Params(ctypes.Structure):
     _fields_ = [("c_puct", ctypes.c_float), ("noise_eps", ctypes.c_float), ("dirichlet_alpha", ctypes.c_float),
                 ("max_game_length", ctypes.c_int32), ("mode", ctypes.c_int32), ("virtual_loss", ctypes.c_float)]
@@ -61,13 +84,21 @@ class TreeSearch:
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  c_puct=0.7, noise_eps=0.25, dirichlet_alpha=0.3, max_nodes=None, transpositions=True, mode=PUCT,
                  virtual_loss=None, max_game_length=None, skip_unread_rows=True, share_equal_leaves=True, reuse_store=0,
-                 keep_tree=False):
+                 keep_tree=False, rolling=False):
         """mode = PUCT: woker/solo_play.py::HivePlayer; mode = UCT: alpha_zero/MCTS_chess.py::UCT_search (plain tree, no
         noise, no length cap; with one slot the virtual loss is 0 so that W sums exactly like the sequential reference).
 
         keep_tree: search(..., played=...) starts from the subtree under the move that was played since the previous
         search (hive_search_advance_roots) instead of from an empty tree; a tree that would leave fewer than
-        sims + slots + 2 of the max_nodes (default then: 3 * sims + slots + 2) free is dropped (carry_stats)."""
+        sims + slots + 2 of the max_nodes (default then: 3 * sims + slots + 2) free is dropped (carry_stats).
+
+        rolling: every game runs on its own clock (hive_search_set_rolling): restart() puts some games onto new roots while
+        the others go on, run_rounds() advances every game by one round of `slots` simulations of its own search, and
+        policy_where() answers the games that are done.  A game ends its search with the tree the lock-step search of its
+        budget gives it, bit for bit.  Needs budgets (set_budgets); not with keep_tree, whose advance moves all trees at
+        once.  search() / run_simulations() are the lock-step paths and stay as they are."""
+        if rolling and keep_tree:
+            raise ValueError("TreeSearch: rolling cannot keep trees (hive_search_advance_roots moves every tree at once)")
         L = load()
         if L.hive_device_count() <= 0 or not torch.cuda.is_available():
             raise _lib.HiveError(-2, "no HIP device visible: hive_alphazero_amd has no CPU path")
@@ -85,6 +116,12 @@ class TreeSearch:
         if self.keep_tree:
             check(L.hive_search_set_carry_room(self._h, sims + slots + 2))
             self._unrelated = torch.full((games,), -3, dtype=torch.int32, device=self.device)
+        self.rolling = bool(rolling)
+        if self.rolling:
+            check(L.hive_search_set_rolling(self._h, 1))
+            self.done = torch.zeros((games,), dtype=torch.int8, device=self.device)
+            self.root_feat = torch.zeros((games, 144), dtype=torch.int64, device=self.device)
+            self._clock = torch.zeros((games,), dtype=torch.int32, device=self.device)
         self.mode = mode
         if mode == UCT:
             noise_eps, transpositions = 0.0, False
@@ -288,6 +325,69 @@ class TreeSearch:
         check(L.hive_search_policy(self._h, _p(self.policy), _p(self.action), _p(self.sum_n), 1 if selfplay else 0))
         return self.action, self.policy, self.sum_n
 
+    # ---- rolling: every game on its own clock
+    def _need_rolling(self):
+        if not self.rolling:
+            raise ValueError("TreeSearch: this call needs rolling=True")
+
+    def restart(self, which, root_boards, root_hist, active=None):
+        """The games with which[g] != 0 (int8 / bool [games]) start a new search from root_boards[g] / root_hist[g], clock 0;
+        every other game keeps its tree and its clock (hive_search_restart)."""
+        self._need_rolling()
+        which = torch.as_tensor(which).to(device=self.device, dtype=torch.int8).contiguous()
+        assert which.numel() == self.games
+        self._stream()
+        check(self.L.hive_search_restart(self._h, _p(which), _p(root_boards), _p(root_hist), _p(active)))
+
+    def run_rounds(self, rounds, keep_root_planes=False):
+        """`rounds` rounds: every game that still has budget runs up to `slots` simulations of its own search per round (the
+        root-opening one alone).  -> done int8[games] after the last round (a buffer of this object).
+        keep_root_planes: root_feat int64[games,144] takes the packed feature words of the roots opened in these rounds --
+        at clock 0 a game's slot-0 leaf is its root.  Restarts happen between calls, so only the first round can open one."""
+        self._need_rolling()
+        L, G, k = self.L, self.games, self.slots
+        s = self._stream()
+        n = k * G
+        for r in range(rounds):
+            if keep_root_planes and r == 0:
+                check(L.hive_search_clocks(self._h, _p(self._clock)))
+            for sl in range(k):
+                check(L.hive_search_select(self._h, sl, _p(self.leaf_boards[sl * G:]), _p(self.leaf_hist[sl * G:])))
+            check(L.hive_leaf_launch(_p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.planes), dtype_code(self.plane_dtype),
+                                     HWC, _p(self.workspace), _p(self.leaf_mask), _p(self.leaf_count),
+                                     _p(self.leaf_over), _p(self.leaf_winner), s))
+            if keep_root_planes and r == 0:
+                torch.where((self._clock == 0).view(G, 1), self.workspace[:G * 144].view(G, 144), self.root_feat,
+                            out=self.root_feat)
+            p, v = self._evaluate(k, n, s)
+            p = p.float().contiguous()
+            v = v.float().contiguous().view(-1)
+            for sl in range(k):
+                o = sl * G
+                check(L.hive_search_backup(self._h, sl, _p(self.leaf_boards[o:]), _p(self.leaf_hist[o:]),
+                                           _p(self.leaf_mask[o:]), _p(self.leaf_over[o:]), _p(self.leaf_winner[o:]),
+                                           _p(p[o:]), _p(v[o:])))
+            check(L.hive_search_round_end(self._h, k, _p(self.done)))
+        return self.done
+
+    def policy_where(self, which, selfplay=False):
+        """search()'s answer for the games with which[g] != 0; every other game gets a zero row, action -2 and sum 0
+        (hive_search_policy_where).  -> (action, policy, sum_n), buffers of this object."""
+        which = torch.as_tensor(which).to(device=self.device, dtype=torch.int8).contiguous()
+        assert which.numel() == self.games
+        self._stream()
+        check(self.L.hive_search_policy_where(self._h, _p(which), _p(self.policy), _p(self.action), _p(self.sum_n),
+                                              1 if selfplay else 0))
+        return self.action, self.policy, self.sum_n
+
+    def clocks(self):
+        """int32[games]: the simulations every game's current search has run (hive_search_clocks)."""
+        self._need_rolling()
+        out = torch.zeros((self.games,), dtype=torch.int32, device=self.device)
+        self._stream()
+        check(self.L.hive_search_clocks(self._h, _p(out)))
+        return out
+
     def set_game_ids(self, ids):
         """Global game index per tree (int64[games]): the only per-game key of the noise streams (hive_search.h)."""
         ids = torch.as_tensor(ids, dtype=torch.int64, device=self.device).contiguous()
@@ -367,6 +467,8 @@ class ArenaSearch(TreeSearch):
             raise ValueError("ArenaSearch: reuse_store keeps evaluations by position alone, not by network")
         if options.get("keep_tree"):
             raise ValueError("ArenaSearch: keep_tree would hand one network's evaluations to the other, whose ply is next")
+        if options.get("rolling"):
+            raise ValueError("ArenaSearch: rolling is not built for the arena (both sides' searches run in lock step)")
         super().__init__(games, sims, evaluator_a, device, slots, seed, plane_dtype, **options)
         self.evaluator_a, self.evaluator_b = evaluator_a, evaluator_b
         assert a_white.dtype == torch.int8 and a_white.numel() == games and a_white.is_cuda and a_white.is_contiguous()
@@ -450,11 +552,20 @@ class SelfPlay:
     simulations; a fast ply is searched without root noise (quiet_fast, default True).  Move selection is unchanged.  A fast
     ply stays a row of its game, marked 0 in the packed batch's `full` key (records.FULL_KEY): datasets and the replay
     window take the rows marked 1.  With keep_records this needs packed_records=True -- the 6-tuples of the row-wise
-    route have no room for the flag.  p_full = 1 with full == fast == sims plays the plain engine's games bit for bit."""
+    route have no room for the flag.  p_full = 1 with full == fast == sims plays the plain engine's games bit for bit.
+
+    rolling = True or {"quantum": q} (default None: lock step): every game moves when its OWN search is done.  play_ply() is
+    then one turn-over: q rounds of the rolling search (TreeSearch.run_rounds), the games whose search is complete move and
+    log their ply, and each of them -- and every slot that took a new game -- draws its next budget and starts its next
+    search in the following round while its neighbours go on with theirs.  With a playout cap no round then waits for the
+    full plies: q defaults to the rounds of the shorter search, 1 + ceil((min(full, fast) - 1) / slots).  `plies` counts
+    turn-overs in this mode, not plies of a game; the log entry of a turn-over holds the games that moved in it.  Every
+    game's record is, bit for bit, the record the lock-step engine gives that game id (without playout_cap: the plain
+    engine's).  Not with search_options keep_tree (ValueError)."""
 
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  keep_records=True, game_ids=None, max_finished_kept=1024, report_every=0, log=print, packed_records=False,
-                 search_options=None, playout_cap=None):
+                 search_options=None, playout_cap=None, rolling=None):
         import itertools
         from .batch import BoardBatch
         self.playout_cap = None
@@ -474,8 +585,21 @@ class SelfPlay:
         self.games, self.sims, self.seed = games, sims, int(seed)
         self.env = BoardBatch(games, device)
         self.device = self.env.device
+        self.rolling = None
+        if rolling:
+            opt = {} if rolling is True else dict(rolling)
+            if set(opt) - {"quantum"}:
+                raise ValueError("rolling takes True or {'quantum': rounds per turn-over}")
+            if (search_options or {}).get("keep_tree"):
+                raise ValueError("SelfPlay: rolling cannot keep trees (hive_search_advance_roots moves every tree at once)")
+            shortest = min(self.playout_cap["full"], self.playout_cap["fast"]) if self.playout_cap else sims
+            q = int(opt.get("quantum") or rolling_quantum(shortest, slots))
+            if q < 1:
+                raise ValueError("rolling: quantum must be at least 1")
+            self.rolling = {"quantum": q}
         self.search = TreeSearch(games, sims, evaluator, self.device.index, slots, seed, plane_dtype,
-                                 **(search_options or {}))      # e.g. skip_unread_rows / share_equal_leaves = False
+                                 **dict(search_options or {}, **({"rolling": True} if self.rolling else {})))
+        # (search_options: e.g. skip_unread_rows / share_equal_leaves = False)
         # keep_tree: the action every slot stepped at the last ply (-3 = none: a new game, or the slot did not move)
         self._played = (torch.full((games,), -3, dtype=torch.int32, device=self.device) if self.search.keep_tree else None)
         self.keep_records = keep_records
@@ -504,6 +628,19 @@ class SelfPlay:
             self.budget = torch.zeros((games,), dtype=torch.int32, device=self.device)
             self.full = torch.zeros((games,), dtype=torch.int8, device=self.device)
             self.quiet = torch.zeros((games,), dtype=torch.int8, device=self.device) if self.playout_cap["quiet_fast"] else None
+        if self.rolling:
+            dev = self.device
+            if self.playout_cap is not None:
+                # hive_search_draw_budgets draws every game (and zeroes the idle ones): into scratch, merged under the mask
+                self._draw = (torch.zeros_like(self.budget), torch.zeros_like(self.quiet) if self.quiet is not None else None,
+                              torch.zeros_like(self.full))
+            else:
+                self.budget, self.quiet = torch.full((games,), sims, dtype=torch.int32, device=dev), None
+            self.search.set_budgets(self.budget, self.quiet)
+            assert self.search._budgets.data_ptr() == self.budget.data_ptr()        # the handle reads THESE arrays at every select
+            self._root_boards = torch.zeros((games, 64), dtype=torch.uint8, device=dev)
+            self._root_hist = torch.zeros((games, 384), dtype=torch.uint8, device=dev)
+            self._restart = torch.ones((games,), dtype=torch.bool, device=dev)      # slots whose next search starts at the next turn-over
 
     def stagger(self, seed=0):
         """Spread the games over plies 0..53 with uniformly random legal moves so that a timed window
@@ -616,7 +753,10 @@ class SelfPlay:
     def play_ply(self, forced=None):
         """One move for every game.  Returns the number of games that finished before this move.
         forced: optional int32[games]; entries >= -1 replace the searched move of that slot (replaying a recorded game
-        through the record path; -2 = keep the search's choice)."""
+        through the record path; -2 = keep the search's choice).
+        rolling: one turn-over -- the games whose search is complete move, the others go on searching (class docstring)."""
+        if self.rolling:
+            return self._play_turnover(forced)
         nd = self._retire_finished()
         boards, hist = self.env.export_state()
         if self._copy_done is not None:
@@ -679,6 +819,72 @@ class SelfPlay:
         self.env.step(action, sync=False)
         if self._played is not None:
             self._played = torch.where(action == -2, torch.full_like(action, -3), action)
+        self.plies += 1
+        return nd
+
+    def _play_turnover(self, forced=None):
+        """play_ply() of the rolling engine."""
+        L, G, search = self.search.L, self.games, self.search
+        nd = self._retire_finished()
+        boards, hist = self.env.export_state()
+        if self._copy_done is not None:
+            # the policy, root and flag buffers are rewritten below: they wait for the previous turn-over's record copy
+            torch.cuda.current_stream(self.device).wait_event(self._copy_done)
+        # the games that moved at the last turn-over, and the slots that took a new game since (they moved too: a game ends
+        # by a move), draw their budgets and start their next search; every other game keeps its own
+        w = self._restart
+        if self.playout_cap is not None:
+            cap = self.playout_cap
+            budget, quiet, full = self._draw
+            check(L.hive_search_draw_budgets(ctypes.c_uint64(self.seed & (2 ** 64 - 1)), _p(self.game_id), _p(boards),
+                                             _p(self.active), G, cap["full"], cap["fast"], cap["threshold"], _p(budget),
+                                             _p(quiet), _p(full), stream_ptr(self.device)))
+            torch.where(w, budget, self.budget, out=self.budget)
+            torch.where(w, full, self.full, out=self.full)
+            if quiet is not None:
+                torch.where(w, quiet, self.quiet, out=self.quiet)
+        torch.where(w.view(G, 1), boards, self._root_boards, out=self._root_boards)
+        torch.where(w.view(G, 1), hist, self._root_hist, out=self._root_hist)
+        search.restart(w, self._root_boards, self._root_hist, self.active)
+        done = search.run_rounds(self.rolling["quantum"], keep_root_planes=self.keep_records)
+        action, policy, sum_n = search.policy_where(done, selfplay=True)
+        if self.keep_records:
+            roots, rhist = self._root_boards, self._root_hist
+            mover = (1 - (roots[:, 33] & 1)).to(torch.int8)
+            feat = search.root_feat
+            self.records.append((feat.clone(), policy.clone(), mover, self.game_id.clone()))
+            if len(self.records) > 8:
+                self.records.pop(0)
+            # the record route of play_ply: whole arrays leave on the side stream, the rows of the games that moved are cut
+            # out when a game ends (PlyLog).  The entry holds the roots the finished searches started from.
+            moved = action != -2
+            src = {"feat": feat, "policy": policy, "boards": roots, "hist": rhist, "moved": moved}
+            if self.playout_cap is not None:
+                src["full"] = self.full
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(self.device))
+            prev_copy = self._copy_done
+            host = self._pinned_pool.pop() if self._pinned_pool else \
+                {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True) for k, v in src.items()}
+            with torch.cuda.stream(self._copy_stream):
+                self._copy_stream.wait_event(ready)
+                for k, v in src.items():
+                    host[k].copy_(v, non_blocking=True)
+                    v.record_stream(self._copy_stream)
+                self._copy_done = torch.cuda.Event()
+                self._copy_done.record(self._copy_stream)
+            log = self._plylog
+            log.append(self.plies, keepalive=host, **{k: v.numpy() for k, v in host.items()})
+            if len(log.entries) >= 2 and prev_copy is not None:
+                prev_copy.synchronize()
+                freed = log.settle(log.entries[-2])
+                if freed is not None:
+                    self._pinned_pool.append(freed)
+        if forced is not None:
+            forced = torch.as_tensor(forced, dtype=torch.int32, device=self.device)
+            action = torch.where((forced >= -1) & (action != -2), forced, action)
+        self.env.step(action, sync=False)
+        self._restart = action != -2
         self.plies += 1
         return nd
 

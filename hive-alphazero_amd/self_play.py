@@ -115,7 +115,8 @@ def _game_worker(rank, world, cfg, out):
         # finished_games at once, so the keep limit must cover the whole batch (this loop drains after every ply)
         compact = cfg["row_format"] == "compact"
         sp = mcts.SelfPlay(cfg["games_per_gpu"], cfg["sims"], evaluator, device=0, slots=cfg["slots"], seed=cfg["seed"],
-                           game_ids=ids, max_finished_kept=max(1024, 2 * cfg["games_per_gpu"]), packed_records=True)
+                           game_ids=ids, max_finished_kept=max(1024, 2 * cfg["games_per_gpu"]), packed_records=True,
+                           playout_cap=cfg.get("playout_cap"), rolling=cfg.get("rolling"))
         out.put(("ready", rank, time.time(), 0, dict(evaluator.precision_report)))
         spool = spool_dir() if cfg.get("spool", True) else None
         while True:
@@ -145,12 +146,14 @@ class SelfPlayWorker:
     """The multi-GPU self-play producer: one child process and one mcts.SelfPlay engine per GPU, the parent gathers their
     packed batches and writes the files.
 
-    No playout_cap option here yet: every ply of every game gets `sims` simulations (mcts.SelfPlay(playout_cap=...) is the
-    single-engine route).  The hand-over formats do carry the optional `full` key of a packed batch when a batch has it."""
+    playout_cap / rolling are handed to every child's mcts.SelfPlay as they are (see there: playout-cap randomisation with
+    `sims` = max(full, fast); every game moving when its own search is done).  Both need row_format="compact": the packed
+    hand-over carries the `full` key of a capped batch, the reference's JSON rows have no room for it, and a rolling child
+    hands over games one by one as they end."""
 
     def __init__(self, total_games, games_per_gpu=1024, sims=50, gpus=None, seed=0, net_seed=0, checkpoint=None, slots=1,
                  datapath="../dataSelf", games_per_file=100, report_every=10, worker=_game_worker, log=print, row_format="json",
-                 net_dtype="auto", warmup=False, keep_results=True, spool=True):
+                 net_dtype="auto", warmup=False, keep_results=True, spool=True, playout_cap=None, rolling=None):
         """row_format "json": results / files hold the reference's rows (play_<ts>.json, self_play.py:100-112);
         "compact": results hold the games as SelfPlay collects them and the files are play_<ts>.npz (records.save_games;
         records.dataset_from_games / rows_from_game expand them) -- the format that keeps up with a node of GPUs."""
@@ -159,11 +162,15 @@ class SelfPlayWorker:
         self_play.py:54-75).  spool: children hand finished waves over as tmpfs files (spool_dir) instead of pickles."""
         if row_format not in ("json", "compact"):
             raise ValueError("row_format must be 'json' or 'compact'")
+        if (playout_cap is not None or rolling) and row_format != "compact":
+            raise ValueError("SelfPlayWorker: playout_cap / rolling need row_format='compact'")
         self.keep_results = bool(keep_results) or row_format != "compact"
         self.row_format = row_format
         self.cfg = {"total_games": int(total_games), "games_per_gpu": int(games_per_gpu), "sims": int(sims), "seed": int(seed),
                     "net_seed": int(net_seed), "checkpoint": checkpoint, "slots": int(slots), "row_format": row_format,
-                    "net_dtype": net_dtype, "warmup": bool(warmup), "spool": bool(spool)}
+                    "net_dtype": net_dtype, "warmup": bool(warmup), "spool": bool(spool),
+                    "playout_cap": dict(playout_cap) if playout_cap is not None else None,
+                    "rolling": (dict(rolling) if isinstance(rolling, dict) else bool(rolling)) if rolling else None}
         if gpus is None:
             import torch
             gpus = list(range(torch.cuda.device_count()))      # counting devices does not initialise HIP

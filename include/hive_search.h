@@ -181,6 +181,39 @@ int hive_search_draw_budgets(uint64_t seed, const int64_t *game_id, const HiveBo
                              int full_sims, int fast_sims, uint32_t full_threshold, int32_t *budget, int8_t *quiet, int8_t *full,
                              void *stream);
 
+/* ---- Rolling search: every game on its own clock.
+ *
+ * on != 0 gives the handle a device int32 clock[games] (zeroed by this call): clock[g] = the simulations game g's current
+ * search has run, in place of the one host counter that numbers the simulations of a lock-step batch.  A round is then
+ *   hive_search_select(slot 0 .. slots-1) -> leaves, network -> hive_search_backup(slot 0 .. slots-1) -> hive_search_round_end
+ * and with c = clock[g], b = budget[g] (hive_search_set_budgets: required, hive_search_select returns HIVE_E_ARG without)
+ * game g takes part in slot sl iff it is active, c + sl < b and (c > 0 or sl == 0) -- the root-opening simulation runs
+ * alone, as in a lock-step search.  Otherwise the slot treats it exactly as an inactive game: no leaf, path length 0, no
+ * virtual loss, no histogram entry.  Its simulation number for the noise key is c + sl: 0 alone, then 1 + sl,
+ * 1 + slots + sl, ... -- the numbers a lock-step search gives the same simulations, so game g ends its search with the tree
+ * a lock-step search of budget[g] simulations gives it, bit for bit, whatever its neighbours do meanwhile.
+ * The caller changes budget[g] / quiet[g] only between a `done` for game g and its restart.
+ * hive_search_set_roots restarts every game (clocks 0); hive_search_advance_roots returns HIVE_E_ARG while on: it moves all
+ * trees at once.  on == 0 goes back to the host counter. */
+int hive_search_set_rolling(HiveSearch *s, int on);
+
+/* After the backups of a round of `slots_run` slots: an active game with clock < budget advances by 1 if its clock was 0,
+ * else by min(slots_run, budget - clock).  done = int8[games]: 1 for an active game whose clock has reached its budget (it
+ * stays 1, and the game sits out, until hive_search_restart), 0 for every other game. */
+int hive_search_round_end(HiveSearch *s, int slots_run, int8_t *done);
+
+/* hive_search_set_roots for the games with which[g] != 0 (int8[games]) alone: root, empty tree and table, active flag,
+ * clock 0; boards / hist / active are read at those games only.  Every other game keeps every byte of its state. */
+int hive_search_restart(HiveSearch *s, const int8_t *which, const HiveBoard *boards, const HiveHistory *hist,
+                        const int8_t *active);
+
+/* hive_search_policy for the games with which[g] != 0 (int8[games]); every other game is answered as an inactive one:
+ * zero policy row, action -2, sum_n 0.  With or without hive_search_set_rolling. */
+int hive_search_policy_where(HiveSearch *s, const int8_t *which, float *policy, int32_t *action, int32_t *sum_n, int selfplay);
+
+/* The clocks, copied into device int32[games]. */
+int hive_search_clocks(HiveSearch *s, int32_t *clock);
+
 /* The search's own noise generator, exposed for statistical tests: draw d (= 0 .. draws-1) is what the root of game id
  * `first_game + d` would get at (turn, sim 0, slot 0): eta ~ Dirichlet(alpha) over k <= HIVE_EDGE_CAP edges
  * (solo_play.py:322-323, np.random.dirichlet).  out = float[draws][k]; prior = float[k] or NULL:
