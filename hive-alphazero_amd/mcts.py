@@ -71,6 +71,25 @@ def rolling_quantum(sims, slots):
     return 1 + -(-(int(sims) - 1) // int(slots))
 
 
+def rolling_options(rolling, search_options, sims, slots, playout_cap=None):
+    """SelfPlay's `rolling` argument checked and completed (no GPU): None for lock step, else {"quantum": rounds per
+    turn-over}.  rolling = None / False, True, or {"quantum": q}; the default quantum is the rounds of the shorter search,
+    rolling_quantum(min(full, fast) with a cap else sims, slots).  search_options with keep_tree are refused with rolling:
+    hive_search_advance_roots moves every tree at once."""
+    if not rolling:
+        return None
+    opt = {} if rolling is True else dict(rolling)
+    if set(opt) - {"quantum"}:
+        raise ValueError("rolling takes True or {'quantum': rounds per turn-over}")
+    if (search_options or {}).get("keep_tree"):
+        raise ValueError("SelfPlay: rolling cannot keep trees (hive_search_advance_roots moves every tree at once)")
+    shortest = min(playout_cap["full"], playout_cap["fast"]) if playout_cap else sims
+    q = int(opt.get("quantum") or rolling_quantum(shortest, slots))
+    if q < 1:
+        raise ValueError("rolling: quantum must be at least 1")
+    return {"quantum": q}
+
+
 class _Params(ctypes.Structure):
     _fields_ = [("c_puct", ctypes.c_float), ("noise_eps", ctypes.c_float), ("dirichlet_alpha", ctypes.c_float),
                 ("max_game_length", ctypes.c_int32), ("mode", ctypes.c_int32), ("virtual_loss", ctypes.c_float)]
@@ -585,18 +604,7 @@ class SelfPlay:
         self.games, self.sims, self.seed = games, sims, int(seed)
         self.env = BoardBatch(games, device)
         self.device = self.env.device
-        self.rolling = None
-        if rolling:
-            opt = {} if rolling is True else dict(rolling)
-            if set(opt) - {"quantum"}:
-                raise ValueError("rolling takes True or {'quantum': rounds per turn-over}")
-            if (search_options or {}).get("keep_tree"):
-                raise ValueError("SelfPlay: rolling cannot keep trees (hive_search_advance_roots moves every tree at once)")
-            shortest = min(self.playout_cap["full"], self.playout_cap["fast"]) if self.playout_cap else sims
-            q = int(opt.get("quantum") or rolling_quantum(shortest, slots))
-            if q < 1:
-                raise ValueError("rolling: quantum must be at least 1")
-            self.rolling = {"quantum": q}
+        self.rolling = rolling_options(rolling, search_options, sims, slots, self.playout_cap)
         self.search = TreeSearch(games, sims, evaluator, self.device.index, slots, seed, plane_dtype,
                                  **dict(search_options or {}, **({"rolling": True} if self.rolling else {})))
         # (search_options: e.g. skip_unread_rows / share_equal_leaves = False)
