@@ -139,10 +139,14 @@ class Arena:
     sims_b (default None: both sides search `sims` simulations): the sides search unequally, A with `sims` and B with
     `sims_b` simulations per move.  The batch then runs max(sims, sims_b) simulations and every game drops out of it after
     its owner's share (hive_arena_budget_launch at every ply + the search's per-game budgets); rows_evaluated() shows what
-    each side cost.  The first use: how much stronger is one network with 50 simulations than with 10."""
+    each side cost.  The first use: how much stronger is one network with 50 simulations than with 10.
+
+    gumbel_a / gumbel_b (None | True | {"m", "c_visit", "c_scale"}): that side searches with the Gumbel root and plays
+    argmax(g + logit + sigma(q)) (mcts.ArenaSearch); the other side's searches are untouched."""
 
     def __init__(self, evaluator_a, evaluator_b, pairs=512, sims=50, slots=1, games_in_flight=1024, seed=0, opening_turns=4,
-                 noise_eps=0.0, pair_ids=None, keep_moves=True, device=None, search_options=None, sims_b=None):
+                 noise_eps=0.0, pair_ids=None, keep_moves=True, device=None, search_options=None, sims_b=None,
+                 gumbel_a=None, gumbel_b=None):
         import torch
         from . import mcts
         from .batch import BoardBatch
@@ -163,7 +167,7 @@ class Arena:
         self.pair_id = torch.zeros((G,), dtype=torch.int64, device=dev)
         rounds = sims if self.sims_b is None else max(sims, self.sims_b)
         self.search = mcts.ArenaSearch(G, rounds, evaluator_a, evaluator_b, self.a_white, dev.index, slots, seed,
-                                       noise_eps=noise_eps, **(search_options or {}))
+                                       noise_eps=noise_eps, gumbel_a=gumbel_a, gumbel_b=gumbel_b, **(search_options or {}))
         self.budget = torch.zeros((G,), dtype=torch.int32, device=dev) if self.sims_b is not None else None
         self._assign()
         self.result_codes = torch.zeros((G,), dtype=torch.int8, device=dev)

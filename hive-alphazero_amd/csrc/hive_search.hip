@@ -50,6 +50,11 @@ struct SearchDev {
     const int8_t *quiet;                           // [G] != 0: no root noise for that game, or nullptr
     int32_t *clock;                                // [G] simulations of its own search each game has run, or nullptr: one
                                                    // host counter for the whole batch (hive_search_set_rolling)
+    float *root_v;                                 // [G] the network's value of the root position (search_backup_kernel, LEAF_ROOT)
+    int gum_on;                                    // hive_search_set_gumbel: the Gumbel root is on ...
+    HiveGumbelParams gum;
+    const int8_t *gum_where;                       // ... for the games with gum_where[g] != 0 (nullptr: for every game)
+    int32_t *gum_fallback;                         // [G] root selections that found no edge at the scheduled visit count
 };
 
 // the node arrays of one pool: hive_search_advance_roots moves the kept subtrees from the handle's pool into a second one
@@ -137,6 +142,117 @@ __device__ __forceinline__ float uct_score(float w, float n, float p, float sqrt
     const float q = w / d;
     const float u = sqrt_visits * (fabsf(p) / d);
     return q + u;
+}
+
+// ------------------------------------------------------------------ Gumbel root (include/hive_search.h, hive_search_set_gumbel)
+constexpr unsigned long long kGumbelStream = 0x6A09E667F3BCC909ull;
+
+__device__ __forceinline__ bool gumbel_game(const SearchDev &S, int g)
+{
+    return S.gum_on && S.prm.mode != HIVE_SEARCH_UCT && (S.gum_where == nullptr || S.gum_where[g] != 0);
+}
+
+// entry i of the sequential-halving sequence of considered visits for m >= 1 considered actions and n simulations: the
+// phases are walked arithmetically.  In a phase the first k slots all hold the same count `base` (k only shrinks, and every
+// emission increments all of the first k), so a phase is `extra` runs of k equal entries base, base + 1, ...
+__device__ __forceinline__ int gumbel_considered_visit(int m, int n, int i)
+{
+    if (m <= 1) return i;
+    int L = 0;
+    while ((1 << L) < m) ++L;
+    int k = m, base = 0, pos = 0;
+    while (true) {                                              // every phase emits at least 2 entries: at most i / 2 rounds
+        int extra = n / (L * k);
+        if (extra < 1) extra = 1;
+        const int len = extra * k;
+        if (i < pos + len) return base + (i - pos) / k;
+        pos += len;
+        base += extra;
+        k = k / 2 > 2 ? k / 2 : 2;
+    }
+}
+
+// sigma(q~) and the score of one edge, fp32 without contraction like uct_score
+__device__ __forceinline__ float gumbel_sigma(float c_visit, float c_scale, float max_n, float qn)
+{
+#pragma clang fp contract(off)
+    return (c_visit + max_n) * c_scale * qn;
+}
+__device__ __forceinline__ float gumbel_score(float g, float logit, float sigma)
+{
+#pragma clang fp contract(off)
+    const float a = g + logit;
+    return a + sigma;
+}
+
+// The per-edge quantities of a Gumbel root, edge e = lane + 64 k in slot k: g, logit, completed q, sigma and the visits.
+// nv[k] = -1 marks a slot past the last edge.  max_n / sum_n are wave-uniform.
+__device__ __forceinline__ void wave_gumbel_root(const SearchDev &S, int g, long long eb, int ne, unsigned root_turn, bool quiet,
+                                                 int lane, float gum[4], float logit[4], float qhat[4], float sigma[4], int nv[4],
+                                                 int &max_n, int &sum_n)
+{
+    int nsum = 0, nmax = 0;
+    float pq = 0.f, pv = 0.f;
+    for (int k = 0; k < 4; ++k) {
+        const int e = lane + 64 * k;
+        gum[k] = logit[k] = qhat[k] = sigma[k] = 0.f;
+        nv[k] = -1;
+        if (e < ne) {
+            const float p = S.e_p[eb + e];
+            const int n = S.e_n[eb + e];
+            nv[k] = n;
+            logit[k] = logf(fmaxf(p, 1e-30f));
+            if (!quiet) {
+                Rng r = noise_rng(S.seed ^ kGumbelStream, S.game_id[g], root_turn, 0ull, 0, e);
+                gum[k] = -logf(-logf(r.uniform()));
+            }
+            if (n > 0) {
+                qhat[k] = S.e_w[eb + e] / (float)n;
+                pq += p * qhat[k];
+                pv += p;
+                nsum += n;
+                nmax = n > nmax ? n : nmax;
+            }
+        }
+    }
+    nsum = wave_sum_i(nsum);
+    for (int o = 32; o > 0; o >>= 1) { const int x = __shfl_xor(nmax, o); nmax = x > nmax ? x : nmax; }
+    pq = wave_sum(pq);
+    pv = wave_sum(pv);
+    const float v_root = S.root_v[g];
+    // (visited edges whose priors are all zero -- the pass edge -- leave the mixed value at the root's)
+    const float v_mix = (nsum == 0 || !(pv > 0.f)) ? v_root : (v_root + (float)nsum * (pq / pv)) / (1.0f + (float)nsum);
+    float lo = 3.0e38f, hi = -3.0e38f;
+    for (int k = 0; k < 4; ++k)
+        if (nv[k] >= 0) {
+            if (nv[k] == 0) qhat[k] = v_mix;
+            lo = fminf(lo, qhat[k]);
+            hi = fmaxf(hi, qhat[k]);
+        }
+    hi = wave_max(hi);
+    lo = -wave_max(-lo);
+    const float span = fmaxf(hi - lo, 1e-8f);
+    for (int k = 0; k < 4; ++k)
+        if (nv[k] >= 0) sigma[k] = gumbel_sigma(S.gum.c_visit, S.gum.c_scale, (float)nmax, (qhat[k] - lo) / span);
+    max_n = nmax;
+    sum_n = nsum;
+}
+
+// softmax(logit + sigma) over the edges of one root: improved[k] for edge lane + 64 k (0 past the last edge)
+__device__ __forceinline__ void wave_gumbel_improved(const float logit[4], const float sigma[4], const int nv[4], float improved[4])
+{
+    float mx = -3.0e38f;
+    for (int k = 0; k < 4; ++k)
+        if (nv[k] >= 0) mx = fmaxf(mx, logit[k] + sigma[k]);
+    mx = wave_max(mx);
+    float tot = 0.f;
+    for (int k = 0; k < 4; ++k) {
+        improved[k] = nv[k] >= 0 ? expf(logit[k] + sigma[k] - mx) : 0.f;
+        tot += improved[k];
+    }
+    tot = wave_sum(tot);
+    const float inv = tot > 0.f ? 1.0f / tot : 0.f;
+    for (int k = 0; k < 4; ++k) improved[k] *= inv;
 }
 
 // The reference keeps its tree in a dict keyed by GamePlay.state_key (solo_play.py:167-197, env_hive.py:70-94,151-168):
@@ -250,6 +366,7 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
     int node = 0, depth = 0, kind = LEAF_NONE, leafnode = 0, leafedge = 0;
     const unsigned root_turn = reinterpret_cast<const uint8_t *>(st)[33];
     const bool quiet = S.quiet != nullptr && S.quiet[g] != 0;
+    const bool gumbel = gumbel_game(S, g);
     while (true) {
         if (S.node_term[nbase + node]) { kind = LEAF_TERMINAL; leafnode = node; break; }          // game over (solo_play.py:169-180)
         if ((int)reinterpret_cast<const uint8_t *>(st)[33] >= S.prm.max_game_length) { kind = LEAF_CAPDRAW; break; }   // :181-183
@@ -261,28 +378,54 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
         const float xx = sqrtf((float)S.node_sum_n[nbase + node] + 1.0f);
         // fresh Dirichlet noise on the root priors for every simulation (solo_play.py:322-323)
         float noise[4] = {0.f, 0.f, 0.f, 0.f};
-        const bool noisy = depth == 0 && !uct && S.prm.noise_eps > 0.f && !quiet;
+        const bool noisy = depth == 0 && !uct && S.prm.noise_eps > 0.f && !quiet && !gumbel;
         if (noisy)
             wave_dirichlet(noise, ne, S.prm.dirichlet_alpha, S.seed, S.game_id[g], root_turn, sim, slot, lane);
         float best = -3.0e38f;
         int bidx = 0x7FFFFFFF;
-        for (int k = 0; k < 4; ++k) {
-            int e = lane + 64 * k;
-            if (e < ne) {
-                float p = S.e_p[eb + e], w = S.e_w[eb + e];
-                int n = S.e_n[eb + e];
-                float b;
-                if (uct) {
-                    b = uct_score(w, (float)n, p, xx);
-                } else {
-                    float q = n > 0 ? w / (float)n : 0.f;
-                    if (noisy) p = (1.0f - S.prm.noise_eps) * p + S.prm.noise_eps * noise[k];
-                    b = q + S.prm.c_puct * p * xx / (1.0f + (float)n);
+        if (depth == 0 && gumbel) {
+            // Gumbel root: simulation s >= 1 goes to the best-scoring edge among those that hold the visit count the
+            // sequential-halving schedule asks for; below the root the descent is the PUCT of the loop below, without noise
+            float gum[4], logit[4], qhat[4], sigma[4];
+            int nv[4], max_n, sum_n;
+            wave_gumbel_root(S, g, eb, ne, root_turn, quiet, lane, gum, logit, qhat, sigma, nv, max_n, sum_n);
+            const int n_sched = (S.budget != nullptr ? S.budget[g] : S.gum.sims) - 1;
+            const int m_eff = S.gum.max_considered < ne ? S.gum.max_considered : ne;
+            const int t = gumbel_considered_visit(m_eff, n_sched, (int)sim - 1);
+            float all = -3.0e38f;
+            int aidx = 0x7FFFFFFF;
+            for (int k = 0; k < 4; ++k)
+                if (nv[k] >= 0) {
+                    const float b = gumbel_score(gum[k], logit[k], sigma[k]);
+                    if (b > all) { all = b; aidx = lane + 64 * k; }
+                    if (nv[k] == t && b > best) { best = b; bidx = lane + 64 * k; }
                 }
-                if (b > best) { best = b; bidx = e; }
+            wave_argmax(best, bidx);
+            if (bidx == 0x7FFFFFFF) {                        // no edge holds that count (a root visit was taken back): all edges
+                wave_argmax(all, aidx);
+                bidx = aidx;
+                if (lane == 0) S.gum_fallback[g] += 1;
             }
+            if (bidx >= ne) bidx = 0;                        // (scores that are not numbers compare false everywhere)
+        } else {
+            for (int k = 0; k < 4; ++k) {
+                int e = lane + 64 * k;
+                if (e < ne) {
+                    float p = S.e_p[eb + e], w = S.e_w[eb + e];
+                    int n = S.e_n[eb + e];
+                    float b;
+                    if (uct) {
+                        b = uct_score(w, (float)n, p, xx);
+                    } else {
+                        float q = n > 0 ? w / (float)n : 0.f;
+                        if (noisy) p = (1.0f - S.prm.noise_eps) * p + S.prm.noise_eps * noise[k];
+                        b = q + S.prm.c_puct * p * xx / (1.0f + (float)n);
+                    }
+                    if (b > best) { best = b; bidx = e; }
+                }
+            }
+            wave_argmax(best, bidx);
         }
-        wave_argmax(best, bidx);
         int child = S.e_child[eb + bidx];
         if (child == -1 && S.n_nodes[g] + S.L >= S.MN) child = -2;    // node pool exhausted: treat as a collision
         if (lane == 0) {
@@ -441,6 +584,7 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
             }
         }
         if (lane == 0) {
+            if (kind == LEAF_ROOT) S.root_v[g] = v[g];          // the Gumbel root completes unvisited edges with it
             S.node_nedge[nbase + id] = ne;
             S.node_sum_n[nbase + id] = 0;
             S.node_term[nbase + id] = term ? 1 : 0;
@@ -492,6 +636,31 @@ search_policy_kernel(SearchDev S, const int8_t *__restrict__ which, float *__res
     }
     const long long nbase = (long long)g * S.MN, eb = nbase * EC;
     const int ne = S.node_nedge[nbase];
+    if (gumbel_game(S, g)) {
+        // Gumbel root: the move is the best-scoring edge among the most visited, the policy is softmax(logit + sigma(completed
+        // q)) over every edge.  Neither the "every W negative" fallback nor the opening resampling applies.
+        const bool quiet = S.quiet != nullptr && S.quiet[g] != 0;
+        float gum[4], logit[4], qhat[4], sigma[4], improved[4];
+        int nv[4], max_n, visits;
+        wave_gumbel_root(S, g, eb, ne, S.node_board[nbase].turn, quiet, lane, gum, logit, qhat, sigma, nv, max_n, visits);
+        wave_gumbel_improved(logit, sigma, nv, improved);
+        float best = -3.0e38f;
+        int bidx = 0x7FFFFFFF;
+        for (int k = 0; k < 4; ++k)
+            if (nv[k] >= 0) {
+                const int e = lane + 64 * k, a = S.e_act[eb + e];
+                if (pol && a >= 0) pol[a] = improved[k];
+                const float b = gumbel_score(gum[k], logit[k], sigma[k]);
+                if (nv[k] == max_n && b > best) { best = b; bidx = e; }
+            }
+        wave_argmax(best, bidx);
+        if (bidx >= ne) bidx = 0;                               // (scores that are not numbers compare false everywhere)
+        if (lane == 0) {
+            action[g] = S.e_act[eb + bidx];
+            if (sum_n_out) sum_n_out[g] = visits;
+        }
+        return;
+    }
     int nsum = 0;
     float wmax = -3.0e38f;
     for (int k = 0; k < 4; ++k) {
@@ -628,6 +797,43 @@ search_noise_kernel(unsigned long long seed, long long first_game, unsigned turn
     for (int j = 0; j < 4; ++j) {
         const int e = lane + 64 * j;
         if (e < k) out[(long long)d * k + e] = prior ? (1.0f - eps) * prior[e] + eps * noise[j] : noise[j];
+    }
+}
+
+// hive_search_gumbel_schedule: the device's schedule function, entry by entry
+__global__ void __launch_bounds__(256)
+search_gumbel_schedule_kernel(int m, int n, int32_t *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = gumbel_considered_visit(m, n, i);
+}
+
+// hive_search_root_gumbel: the per-edge quantities of every root as search_select_kernel / search_policy_kernel see them
+// now, in edge order; zero rows for a game without a tree, zeros past the last edge
+__global__ void __launch_bounds__(256)
+search_root_gumbel_kernel(SearchDev S, float *__restrict__ gum_out, float *__restrict__ logit_out, float *__restrict__ qhat_out,
+                          float *__restrict__ improved_out)
+{
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= S.G) return;
+    const long long nbase = (long long)g * S.MN, eb = nbase * EC, row = (long long)g * EC;
+    const bool tree = S.active[g] && S.n_nodes[g] > 0 && !S.node_term[nbase];
+    const int ne = tree ? (S.node_nedge[nbase] < EC ? S.node_nedge[nbase] : EC) : 0;
+    float gum[4], logit[4], qhat[4], sigma[4], improved[4];
+    int nv[4] = {-1, -1, -1, -1}, max_n, visits;
+    if (tree) {
+        const bool quiet = S.quiet != nullptr && S.quiet[g] != 0;
+        wave_gumbel_root(S, g, eb, ne, S.node_board[nbase].turn, quiet, lane, gum, logit, qhat, sigma, nv, max_n, visits);
+        wave_gumbel_improved(logit, sigma, nv, improved);
+    }
+    for (int k = 0; k < 4; ++k) {
+        const int e = lane + 64 * k;
+        const bool on = nv[k] >= 0;
+        if (gum_out) gum_out[row + e] = on ? gum[k] : 0.f;
+        if (logit_out) logit_out[row + e] = on ? logit[k] : 0.f;
+        if (qhat_out) qhat_out[row + e] = on ? qhat[k] : 0.f;
+        if (improved_out) improved_out[row + e] = on ? improved[k] : 0.f;
     }
 }
 
@@ -882,6 +1088,10 @@ static int search_alloc(HiveSearch *s, int games, int max_nodes, int slots)
     S_TRY(hipMemset(d.carry_kept, 0, sizeof(int32_t) * (size_t)games));
     S_TRY(hipMemset(d.carry_visits, 0, sizeof(int32_t) * (size_t)games));
     S_TRY(hipMemset(d.carry_refused, 0, sizeof(int32_t) * (size_t)games));
+    S_TRY(alloc(s, &d.root_v, (size_t)games));
+    S_TRY(alloc(s, &d.gum_fallback, (size_t)games));
+    S_TRY(hipMemset(d.root_v, 0, sizeof(float) * (size_t)games));
+    S_TRY(hipMemset(d.gum_fallback, 0, sizeof(int32_t) * (size_t)games));
     {
         long long *ids = new (std::nothrow) long long[games];
         if (ids == nullptr) return hive::set_error(HIVE_E_DEVICE, "hive_search_create: out of host memory");
@@ -950,6 +1160,8 @@ int hive_search_set_params(HiveSearch *s, const HiveSearchParams *p)
     if ((p->mode != HIVE_SEARCH_PUCT && p->mode != HIVE_SEARCH_UCT) || !(p->virtual_loss >= 0.f) || p->max_game_length < 1 ||
         p->max_game_length > 250)
         return hive::set_error(HIVE_E_ARG, "hive_search_set_params: unknown mode, negative virtual loss or length cap outside 1..250");
+    if (s->d.gum_on && p->mode == HIVE_SEARCH_UCT)
+        return hive::set_error(HIVE_E_ARG, "hive_search_set_params: the Gumbel root is on and has no UCT form (hive_search_set_gumbel)");
     s->d.prm = *p;
     return HIVE_OK;
 }
@@ -1022,6 +1234,55 @@ int hive_search_set_budgets(HiveSearch *s, const int32_t *budget, const int8_t *
     return HIVE_OK;
 }
 
+int hive_search_set_gumbel(HiveSearch *s, const HiveGumbelParams *prm, const int8_t *where)
+{
+    if (!s) return hive::set_error(HIVE_E_ARG, "null handle");
+    if (!prm) {
+        s->d.gum_on = 0;
+        s->d.gum_where = nullptr;
+        return HIVE_OK;
+    }
+    if (s->d.prm.mode == HIVE_SEARCH_UCT)
+        return hive::set_error(HIVE_E_ARG, "hive_search_set_gumbel: the Gumbel root has no UCT form (PUCT mode only)");
+    if (s->d.L > 1)
+        return hive::set_error(HIVE_E_ARG, "hive_search_set_gumbel: one slot only -- visits in flight would desynchronise the "
+                                           "sequential-halving schedule");
+    if (prm->max_considered < 1 || !(prm->c_visit >= 0.f) || !(prm->c_scale > 0.f) || prm->sims < 1)
+        return hive::set_error(HIVE_E_ARG, "hive_search_set_gumbel: max_considered and sims must be at least 1, c_visit >= 0, "
+                                           "c_scale > 0");
+    s->d.gum = *prm;
+    s->d.gum_where = where;
+    s->d.gum_on = 1;
+    return HIVE_OK;
+}
+
+int hive_search_gumbel_schedule(int m, int n, int32_t *out_dev, void *stream)
+{
+    if (m < 1 || n < 1 || !out_dev) return hive::set_error(HIVE_E_ARG, "hive_search_gumbel_schedule: bad argument");
+    hipLaunchKernelGGL(search_gumbel_schedule_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m, n,
+                       out_dev);
+    S_TRY(hipGetLastError());
+    return HIVE_OK;
+}
+
+int hive_search_root_gumbel(HiveSearch *s, float *g, float *logit, float *qhat, float *improved)
+{
+    if (!s) return hive::set_error(HIVE_E_ARG, "null handle");
+    if (!s->d.gum_on) return hive::set_error(HIVE_E_ARG, "hive_search_root_gumbel: the Gumbel root is off (hive_search_set_gumbel)");
+    S_TRY(hipSetDevice(s->device));
+    hipLaunchKernelGGL(search_root_gumbel_kernel, wave_grid(s->d.G), dim3(256), 0, s->stream, s->d, g, logit, qhat, improved);
+    S_TRY(hipGetLastError());
+    return HIVE_OK;
+}
+
+int hive_search_gumbel_fallbacks(HiveSearch *s, int32_t *count)
+{
+    if (!s || !count) return hive::set_error(HIVE_E_ARG, "null argument");
+    S_TRY(hipSetDevice(s->device));
+    S_TRY(hipMemcpyAsync(count, s->d.gum_fallback, sizeof(int32_t) * (size_t)s->d.G, hipMemcpyDeviceToDevice, s->stream));
+    return HIVE_OK;
+}
+
 int hive_search_draw_budgets(uint64_t seed, const int64_t *game_id, const HiveBoard *root_boards, const int8_t *active, int n,
                              int full_sims, int fast_sims, uint32_t full_threshold, int32_t *budget, int8_t *quiet, int8_t *full,
                              void *stream)
@@ -1048,6 +1309,9 @@ int hive_search_advance_roots(HiveSearch *s, const int32_t *played, const HiveBo
     if (!s || !boards || !hist) return hive::set_error(HIVE_E_ARG, "null argument");
     if (s->d.clock)
         return hive::set_error(HIVE_E_ARG, "hive_search_advance_roots: not with per-game clocks (hive_search_set_rolling)");
+    if (s->d.gum_on)
+        return hive::set_error(HIVE_E_ARG, "hive_search_advance_roots: not with the Gumbel root (hive_search_set_gumbel): a carried "
+                                           "root has no network value and no fresh schedule");
     S_TRY(hipSetDevice(s->device));
     SearchDev &d = s->d;
     // LDS per game: map + queue, 8 bytes per node; four games per workgroup while that fits into 64 KB, else one

@@ -90,6 +90,102 @@ def rolling_options(rolling, search_options, sims, slots, playout_cap=None):
     return {"quantum": q}
 
 
+# ---- Gumbel root with sequential halving (include/hive_search.h, hive_search_set_gumbel): the numpy statements, no GPU
+GUMBEL_STREAM = 0x6A09E667F3BCC909      # stream constant of the per-edge Gumbel draws
+GUMBEL_DEFAULTS = {"m": 16, "c_visit": 50.0, "c_scale": 1.0}      # c_visit / c_scale: the paper's values, not tuned for this game
+
+
+def gumbel_considered_visits(m, n):
+    """int32[n]: the sequential-halving sequence of considered visits for m considered actions and n simulations (Danihelka
+    et al. 2022, as the published mctx code lays it out).  m <= 1: 0 .. n-1.  Else with L = ceil(log2 m) and k = m: emit
+    max(1, n // (L k)) times the visit counts of the first k slots, incrementing them after each emission, then
+    k = max(2, k // 2), until n entries exist.  Simulation s >= 1 of a search goes to an edge that holds entry s - 1 visits."""
+    import numpy as np
+    m, n = int(m), max(int(n), 0)
+    if m <= 1:
+        return np.arange(n, dtype=np.int32)
+    log2m = (m - 1).bit_length()
+    seq, visits, k = [], [0] * m, m
+    while len(seq) < n:
+        for _ in range(max(1, n // (log2m * k))):
+            seq.extend(visits[:k])
+            for i in range(k):
+                visits[i] += 1
+        k = max(2, k // 2)
+    return np.asarray(seq[:n], dtype=np.int32)
+
+
+def gumbel_draw(seed, game_id, turn, ne, quiet=False):
+    """float64[ne]: g_e = -log(-log(u_e)) of the root of game `game_id` at root turn `turn`; u_e (float32, computed exactly as
+    the device does, like playout_cap_draw's word) is the first uniform of csrc/hive_rng.hpp's generator keyed
+    (seed ^ GUMBEL_STREAM, game id, turn << 40, edge e) -- the noise key at simulation 0, slot 0.  quiet: zeros."""
+    import numpy as np
+    from .replay import _M64, _splitmix
+    ne = int(ne)
+    if quiet:
+        return np.zeros(ne, dtype=np.float64)
+    with np.errstate(over="ignore", divide="ignore"):
+        e = np.arange(ne, dtype=np.uint64)
+        key = np.full(1, (int(seed) ^ GUMBEL_STREAM) & _M64, dtype=np.uint64)
+        a = np.full(1, int(game_id) & _M64, dtype=np.uint64)
+        b = np.full(1, (int(turn) << 40) & _M64, dtype=np.uint64)
+        s = _splitmix(key ^ _splitmix(a * np.uint64(0x100000001B3) + _splitmix(b * np.uint64(0x9E3779B1) + e)))
+        s = _splitmix(s)
+        u = ((s >> np.uint64(40)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+        return -np.log(-np.log(u.astype(np.float64)))
+
+
+def gumbel_improved_policy(p, n, w, v_root, c_visit=GUMBEL_DEFAULTS["c_visit"], c_scale=GUMBEL_DEFAULTS["c_scale"]):
+    """(logit + sigma(completed q), improved policy) float64[ne] of a root with priors p, visits n, value sums w and the
+    network value v_root: the rule of include/hive_search.h in float64.  The score of an edge is its g plus the first array;
+    the improved policy is the softmax of the first array."""
+    import numpy as np
+    p = np.asarray(p, dtype=np.float64)
+    n = np.asarray(n, dtype=np.int64)
+    w = np.asarray(w, dtype=np.float64)
+    logit = np.log(np.maximum(p, 1e-30))
+    seen = n > 0
+    q = np.where(seen, w / np.maximum(n, 1), 0.0)
+    total, prior_seen = int(n.sum()), float(p[seen].sum())
+    v_mix = float(v_root)
+    if total > 0 and prior_seen > 0.0:
+        v_mix = (float(v_root) + total * float((p[seen] * q[seen]).sum()) / prior_seen) / (1.0 + total)
+    qhat = np.where(seen, q, v_mix)
+    lo, hi = float(qhat.min()), float(qhat.max())
+    sigma = (float(c_visit) + int(n.max())) * float(c_scale) * ((qhat - lo) / max(hi - lo, 1e-8))
+    score = logit + sigma
+    z = np.exp(score - score.max())
+    return score, z / z.sum()
+
+
+def gumbel_options(gumbel, slots=1, mode=PUCT, keep_tree=False):
+    """TreeSearch's `gumbel` argument checked and completed (no GPU): None for off, else {"m", "c_visit", "c_scale"}.
+    gumbel = None / False, True, or a dict with any of those keys (GUMBEL_DEFAULTS fill the rest).  Refused, as
+    hive_search_set_gumbel refuses them: slots > 1 (visits in flight would desynchronise the halving schedule), UCT mode,
+    and kept trees (a carried root has no network value of its own and no fresh schedule)."""
+    if not gumbel:
+        return None
+    opt = {} if gumbel is True else dict(gumbel)
+    if set(opt) - set(GUMBEL_DEFAULTS):
+        raise ValueError("gumbel takes True or a dict with m, c_visit, c_scale")
+    opt = {"m": int(opt.get("m", GUMBEL_DEFAULTS["m"])), "c_visit": float(opt.get("c_visit", GUMBEL_DEFAULTS["c_visit"])),
+           "c_scale": float(opt.get("c_scale", GUMBEL_DEFAULTS["c_scale"]))}
+    if opt["m"] < 1 or not opt["c_visit"] >= 0.0 or not opt["c_scale"] > 0.0:
+        raise ValueError("gumbel: m must be at least 1, c_visit >= 0 and c_scale > 0")
+    if int(slots) > 1:
+        raise ValueError("gumbel: one slot only (visits in flight would desynchronise the sequential-halving schedule)")
+    if mode == UCT:
+        raise ValueError("gumbel: the Gumbel root has no UCT form (PUCT mode only)")
+    if keep_tree:
+        raise ValueError("gumbel: not with keep_tree (a carried root has no network value and no fresh schedule)")
+    return opt
+
+
+class _GumbelParams(ctypes.Structure):
+    _fields_ = [("max_considered", ctypes.c_int32), ("c_visit", ctypes.c_float), ("c_scale", ctypes.c_float),
+                ("sims", ctypes.c_int32)]
+
+
 class _Params(ctypes.Structure):
     _fields_ = [("c_puct", ctypes.c_float), ("noise_eps", ctypes.c_float), ("dirichlet_alpha", ctypes.c_float),
                 ("max_game_length", ctypes.c_int32), ("mode", ctypes.c_int32), ("virtual_loss", ctypes.c_float)]
@@ -103,7 +199,7 @@ class TreeSearch:
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  c_puct=0.7, noise_eps=0.25, dirichlet_alpha=0.3, max_nodes=None, transpositions=True, mode=PUCT,
                  virtual_loss=None, max_game_length=None, skip_unread_rows=True, share_equal_leaves=True, reuse_store=0,
-                 keep_tree=False, rolling=False):
+                 keep_tree=False, rolling=False, gumbel=None):
         """mode = PUCT: woker/solo_play.py::HivePlayer; mode = UCT: alpha_zero/MCTS_chess.py::UCT_search (plain tree, no
         noise, no length cap; with one slot the virtual loss is 0 so that W sums exactly like the sequential reference).
 
@@ -115,7 +211,17 @@ class TreeSearch:
         the others go on, run_rounds() advances every game by one round of `slots` simulations of its own search, and
         policy_where() answers the games that are done.  A game ends its search with the tree the lock-step search of its
         budget gives it, bit for bit.  Needs budgets (set_budgets); not with keep_tree, whose advance moves all trees at
-        once.  search() / run_simulations() are the lock-step paths and stay as they are."""
+        once.  search() / run_simulations() are the lock-step paths and stay as they are.
+
+        gumbel = None (default) | True | {"m": 16, "c_visit": 50, "c_scale": 1.0}: the Gumbel root with sequential halving
+        (hive_search_set_gumbel; the rule is stated in include/hive_search.h).  The root's simulations are spent by the
+        halving schedule over the Gumbel-top-m edges instead of by PUCT with Dirichlet noise, the move is
+        argmax(g + logit + sigma(q)) among the most visited edges and the policy is the improved policy
+        softmax(logit + sigma(completed q)), dense over the legal moves, instead of the visit histogram.  Below the root the
+        search is unchanged.  Works with budgets, quiet (g = 0: deterministic) and rolling; refused with slots > 1, UCT and
+        keep_tree (gumbel_options).  c_visit / c_scale are the paper's values and have not been tuned here.
+        set_gumbel_where(mask) restricts it to some games; the others are searched as without it, bit for bit."""
+        gumbel = gumbel_options(gumbel, slots, mode, keep_tree)
         if rolling and keep_tree:
             raise ValueError("TreeSearch: rolling cannot keep trees (hive_search_advance_roots moves every tree at once)")
         L = load()
@@ -153,6 +259,9 @@ class TreeSearch:
         check(L.hive_search_set_params(self._h, ctypes.byref(prm)))
         # the reference's tree is a dict keyed by state_key: positions reached by two move orders share one entry
         check(L.hive_search_set_transpositions(self._h, 1 if transpositions else 0))
+        self.gumbel = self._gumbel_where = self._gumbel_sims = None
+        if gumbel is not None:
+            self.set_gumbel(gumbel)
         n = games * slots
         dev = self.device
         self.plane_dtype = plane_dtype
@@ -286,6 +395,43 @@ class TreeSearch:
         self._budgets, self._quiet = budgets, quiet
         check(self.L.hive_search_set_budgets(self._h, _p(budgets), _p(quiet)))
 
+    def set_gumbel(self, gumbel=True, where=None):
+        """Switch the Gumbel root on (True or the option dict of __init__), for the games with where[g] != 0 (int8 / bool
+        [games]; None = every game), or off (None / False): hive_search_set_gumbel."""
+        opt = gumbel_options(gumbel, self.slots, self.mode, self.keep_tree)
+        if opt is None:
+            check(self.L.hive_search_set_gumbel(self._h, None, None))
+            self.gumbel = self._gumbel_where = self._gumbel_sims = None
+            return
+        if where is not None:
+            where = torch.as_tensor(where).to(device=self.device, dtype=torch.int8).contiguous()
+            assert where.numel() == self.games
+        prm = _GumbelParams(opt["m"], opt["c_visit"], opt["c_scale"], int(self.sims))
+        check(self.L.hive_search_set_gumbel(self._h, ctypes.byref(prm), _p(where)))
+        # (the handle keeps the address of `where`: this object keeps the tensor)
+        self.gumbel, self._gumbel_where, self._gumbel_sims = opt, where, int(self.sims)
+
+    def set_gumbel_where(self, mask):
+        """The games the Gumbel root applies to from now on: int8 / bool [games], None = every game."""
+        if self.gumbel is None:
+            raise ValueError("TreeSearch.set_gumbel_where: the Gumbel root is off (gumbel=... / set_gumbel)")
+        self.set_gumbel(self.gumbel, mask)
+
+    def root_gumbel(self):
+        """(g, logit, completed q, improved policy) fp32[games,256] of the roots as they stand, in edge order (ascending
+        action id; zeros past the last edge): hive_search_root_gumbel."""
+        out = [torch.zeros((self.games, 256), dtype=torch.float32, device=self.device) for _ in range(4)]
+        self._stream()
+        check(self.L.hive_search_root_gumbel(self._h, *[_p(t) for t in out]))
+        return out
+
+    def gumbel_fallbacks(self):
+        """int32[games]: root selections since create that found no edge at the scheduled visit count."""
+        out = torch.zeros((self.games,), dtype=torch.int32, device=self.device)
+        self._stream()
+        check(self.L.hive_search_gumbel_fallbacks(self._h, _p(out)))
+        return out
+
     def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False, played=None, budgets=None,
                quiet=None):
         """-> (action int32[games] (-1 pass, -2 inactive/terminal root), policy fp32[games,1584], sum_n int32[games])
@@ -319,6 +465,8 @@ class TreeSearch:
         """`sims` simulations from the roots as they stand, then the policy: the second half of search()."""
         L, G = self.L, self.games
         s = self._stream()
+        if self.gumbel is not None and self._gumbel_sims != self.sims:      # the schedule's length follows `sims`
+            self.set_gumbel(self.gumbel, self._gumbel_where)
         done = 0
         first = True
         while done < self.sims:
@@ -478,17 +626,30 @@ class ArenaSearch(TreeSearch):
 
     An evaluator without `accepts_need` (a stub, the library path) gets the whole batch.  `rows_evaluated()` = the rows
     each network evaluated; `evals_run` is their sum.  reuse_store is refused: the store's key does not hold the network;
-    keep_tree for the same reason (a kept tree holds the other network's evaluations)."""
+    keep_tree for the same reason (a kept tree holds the other network's evaluations).
+
+    gumbel_a / gumbel_b (None | True | dict, as TreeSearch's gumbel): the side searches with the Gumbel root.  At every search
+    game g is a Gumbel game iff the owner of its search -- the rule above -- has the option; the other side's games are
+    searched as without it, bit for bit.  One handle holds one parameter set: two dicts must be equal."""
 
     def __init__(self, games, sims, evaluator_a, evaluator_b, a_white, device=None, slots=1, seed=0, plane_dtype=None,
-                 **options):
+                 gumbel_a=None, gumbel_b=None, **options):
         if options.get("reuse_store"):
             raise ValueError("ArenaSearch: reuse_store keeps evaluations by position alone, not by network")
         if options.get("keep_tree"):
             raise ValueError("ArenaSearch: keep_tree would hand one network's evaluations to the other, whose ply is next")
         if options.get("rolling"):
             raise ValueError("ArenaSearch: rolling is not built for the arena (both sides' searches run in lock step)")
-        super().__init__(games, sims, evaluator_a, device, slots, seed, plane_dtype, **options)
+        if options.get("gumbel"):
+            raise ValueError("ArenaSearch: give the Gumbel root per side, gumbel_a / gumbel_b")
+        sides = [gumbel_options(x, slots, options.get("mode", PUCT)) for x in (gumbel_a, gumbel_b)]
+        if sides[0] is not None and sides[1] is not None and sides[0] != sides[1]:
+            raise ValueError("ArenaSearch: one handle holds one Gumbel parameter set; gumbel_a and gumbel_b differ")
+        super().__init__(games, sims, evaluator_a, device, slots, seed, plane_dtype,
+                         **dict(options, gumbel=sides[0] or sides[1]))
+        self._gumbel_sides = (sides[0] is not None, sides[1] is not None)
+        if self._gumbel_sides[0] != self._gumbel_sides[1]:      # one side only: the mask is rewritten in place at every search
+            self.set_gumbel_where(torch.zeros((games,), dtype=torch.int8, device=self.device))
         self.evaluator_a, self.evaluator_b = evaluator_a, evaluator_b
         assert a_white.dtype == torch.int8 and a_white.numel() == games and a_white.is_cuda and a_white.is_contiguous()
         self.a_white = a_white
@@ -513,6 +674,10 @@ class ArenaSearch(TreeSearch):
 
     def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False, budgets=None, quiet=None):
         self._roots = root_boards
+        if self._gumbel_where is not None:
+            # the owner of the search of game g (hive_arena_budget_launch's rule): A iff a_white[g] == (root turn is odd)
+            a_owns = (self.a_white != 0) == ((root_boards[:, 33] & 1) != 0)
+            self._gumbel_where.copy_(a_owns if self._gumbel_sides[0] else ~a_owns)
         out = super().search(root_boards, root_hist, active, selfplay, keep_root_planes, budgets=budgets, quiet=quiet)
         torch.sum(self.rows, 0, keepdim=True, out=self.evals_run)
         return out
@@ -580,7 +745,12 @@ class SelfPlay:
     full plies: q defaults to the rounds of the shorter search, 1 + ceil((min(full, fast) - 1) / slots).  `plies` counts
     turn-overs in this mode, not plies of a game; the log entry of a turn-over holds the games that moved in it.  Every
     game's record is, bit for bit, the record the lock-step engine gives that game id (without playout_cap: the plain
-    engine's).  Not with search_options keep_tree (ValueError)."""
+    engine's).  Not with search_options keep_tree (ValueError).
+
+    search_options = {"gumbel": True | {"m", "c_visit", "c_scale"}}: every search uses the Gumbel root (TreeSearch, gumbel).  The
+    move is the root's argmax(g + logit + sigma(q)) -- the opening resampling of turns <= 6 does not apply, the Gumbel draw is
+    the exploration -- and the recorded policy is the improved policy, through the same record route.  In lock step, with
+    playout_cap (a quiet fast ply has g = 0 and is deterministic) and with rolling; one slot, no keep_tree."""
 
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  keep_records=True, game_ids=None, max_finished_kept=1024, report_every=0, log=print, packed_records=False,

@@ -116,7 +116,8 @@ def _game_worker(rank, world, cfg, out):
         compact = cfg["row_format"] == "compact"
         sp = mcts.SelfPlay(cfg["games_per_gpu"], cfg["sims"], evaluator, device=0, slots=cfg["slots"], seed=cfg["seed"],
                            game_ids=ids, max_finished_kept=max(1024, 2 * cfg["games_per_gpu"]), packed_records=True,
-                           playout_cap=cfg.get("playout_cap"), rolling=cfg.get("rolling"))
+                           playout_cap=cfg.get("playout_cap"), rolling=cfg.get("rolling"),
+                           search_options=cfg.get("search_options"))
         out.put(("ready", rank, time.time(), 0, dict(evaluator.precision_report)))
         spool = spool_dir() if cfg.get("spool", True) else None
         while True:
@@ -149,11 +150,13 @@ class SelfPlayWorker:
     playout_cap / rolling are handed to every child's mcts.SelfPlay as they are (see there: playout-cap randomisation with
     `sims` = max(full, fast); every game moving when its own search is done).  Both need row_format="compact": the packed
     hand-over carries the `full` key of a capped batch, the reference's JSON rows have no room for it, and a rolling child
-    hands over games one by one as they end."""
+    hands over games one by one as they end.  search_options (e.g. {"gumbel": True}: the Gumbel root of mcts.TreeSearch) go
+    to every child's SelfPlay(search_options=...) unchanged."""
 
     def __init__(self, total_games, games_per_gpu=1024, sims=50, gpus=None, seed=0, net_seed=0, checkpoint=None, slots=1,
                  datapath="../dataSelf", games_per_file=100, report_every=10, worker=_game_worker, log=print, row_format="json",
-                 net_dtype="auto", warmup=False, keep_results=True, spool=True, playout_cap=None, rolling=None):
+                 net_dtype="auto", warmup=False, keep_results=True, spool=True, playout_cap=None, rolling=None,
+                 search_options=None):
         """row_format "json": results / files hold the reference's rows (play_<ts>.json, self_play.py:100-112);
         "compact": results hold the games as SelfPlay collects them and the files are play_<ts>.npz (records.save_games;
         records.dataset_from_games / rows_from_game expand them) -- the format that keeps up with a node of GPUs."""
@@ -170,7 +173,13 @@ class SelfPlayWorker:
                     "net_seed": int(net_seed), "checkpoint": checkpoint, "slots": int(slots), "row_format": row_format,
                     "net_dtype": net_dtype, "warmup": bool(warmup), "spool": bool(spool),
                     "playout_cap": dict(playout_cap) if playout_cap is not None else None,
-                    "rolling": (dict(rolling) if isinstance(rolling, dict) else bool(rolling)) if rolling else None}
+                    "rolling": (dict(rolling) if isinstance(rolling, dict) else bool(rolling)) if rolling else None,
+                    "search_options": dict(search_options) if search_options else None}
+        if search_options:
+            # refused here, before any child starts, as every child's SelfPlay would refuse it
+            from . import mcts
+            mcts.gumbel_options(search_options.get("gumbel"), int(slots), keep_tree=bool(search_options.get("keep_tree")))
+            mcts.rolling_options(self.cfg["rolling"], search_options, int(sims), int(slots), self.cfg["playout_cap"])
         if gpus is None:
             import torch
             gpus = list(range(torch.cuda.device_count()))      # counting devices does not initialise HIP

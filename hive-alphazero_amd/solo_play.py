@@ -163,6 +163,17 @@ class HivePlayer:
                     todo.append(nxt)
         self._table = kept
 
+    # None: the reference.  A dict switches the root to the Gumbel root with sequential halving, the sequential statement of
+    # hive_search_set_gumbel (the rule: include/hive_search.h): {"m": 16, "c_visit": 50.0, "c_scale": 1.0, "g": ...}.  "g" is
+    # the caller's: an array of one Gumbel draw per root edge (ascending action id), a callable (root turn, edges) -> such an
+    # array (e.g. mcts.gumbel_draw with a seed and game id bound), or None / absent for zeros (a quiet game).  Simulation
+    # s >= 1 takes the best-scoring root edge among those holding the visit count the schedule asks for, action() plays the
+    # best-scoring edge among the most visited and calc_policy() returns the improved policy.  Below the root: PUCT, no noise.
+    # SEARCH_THREADS = 1 only; not with keep_tree.  After action(): gumbel_fallbacks = selections that found no edge at the
+    # scheduled count, gumbel_min_gap = the smallest strictly positive gap between the two best scores over those selections
+    # and the final choice (inf if none).
+    gumbel = None
+
     def action(self, env, non_queue=True):
         if self.keep_tree:
             self.keep_reachable(env)
@@ -170,8 +181,15 @@ class HivePlayer:
             self.reset()
         self.max_depth = env.state.turn
         self.main_key_state = env.state_key
+        if self.gumbel is not None:
+            if self.keep_tree or (self.none_queue and SEARCH_THREADS > 1):
+                raise ValueError("HivePlayer.gumbel: sequential search without kept trees only")
+            self._sim, self._root_v, self._root_g = 0, 0.0, None
+            self.gumbel_fallbacks, self.gumbel_min_gap = 0, float("inf")
         self.search_moves(env)
         policy, visits = self.calc_policy(env)
+        if self.gumbel is not None:
+            return self._gumbel_move(env), [list(policy), visits]
         probs = self.apply_temperature(policy, int(env.state.turn + 1) / 2)
         move = int(np.random.choice(range(ACTION_SPACE), p=probs))
         return move, [list(policy), visits]
@@ -191,6 +209,8 @@ class HivePlayer:
         path = []                      # (entry, edge index) from the root down
         outcome = None
         depth = 0
+        if self.gumbel is not None and is_root_node:
+            self._cur_sim, self._sim = self._sim, self._sim + 1       # simulations of a search are numbered 0, 1, ...
         while True:
             outcome = _terminal_value(env)
             if outcome is not None:
@@ -202,6 +222,8 @@ class HivePlayer:
                     leaf_p, leaf_v = self._evaluate(env)
                     self._table[key] = _Entry(leaf_p)
                     outcome = leaf_v
+                    if self.gumbel is not None and is_root_node and depth == 0:
+                        self._root_v = float(np.asarray(leaf_v).reshape(-1)[0])      # completes the unvisited root edges
                     break
                 edge, move = self._select(entry, env, is_root_node and depth == 0)
                 entry.sum_n += virtual_loss                 # virtual loss (solo_play.py:205-208)
@@ -260,6 +282,8 @@ class HivePlayer:
             return 0, -1
         if entry.moves is None:
             entry.open_edges(legal)
+        if at_root and self.gumbel is not None:
+            return self._gumbel_select(entry, env)
         prior = entry.p
         if at_root:
             noise = np.random.dirichlet([dirichlet_alpha] * len(entry.moves))
@@ -267,6 +291,50 @@ class HivePlayer:
         score = entry.q() + c_puct * prior * np.sqrt(entry.sum_n + 1) / (1 + entry.n)
         edge = int(np.argmax(score))
         return edge, entry.moves[edge]
+
+    # ------------------------------------------------------------------ Gumbel root (sequential statement)
+    def _gumbel_scores(self, entry, env):
+        """(g + logit + sigma, improved policy) over the root's edges."""
+        from .mcts import GUMBEL_DEFAULTS, gumbel_improved_policy
+        opt = self.gumbel
+        if self._root_g is None:
+            g = opt.get("g")
+            if callable(g):
+                g = g(int(env.state.turn), len(entry.moves))
+            self._root_g = np.zeros(len(entry.moves)) if g is None else np.asarray(g, dtype=np.float64)
+            assert self._root_g.shape == (len(entry.moves),)
+        base, improved = gumbel_improved_policy(entry.p, entry.n, entry.w, self._root_v,
+                                                opt.get("c_visit", GUMBEL_DEFAULTS["c_visit"]),
+                                                opt.get("c_scale", GUMBEL_DEFAULTS["c_scale"]))
+        return self._root_g + base, improved
+
+    def _gumbel_best(self, score, eligible):
+        """First maximum of score over the eligible edges (ties to the lower edge); the top-two gap is recorded."""
+        masked = np.where(eligible, score, -np.inf)
+        edge = int(np.argmax(masked))
+        rest = np.delete(masked, edge)
+        if rest.size and np.isfinite(rest.max()) and masked[edge] - rest.max() > 0:
+            self.gumbel_min_gap = min(self.gumbel_min_gap, float(masked[edge] - rest.max()))
+        return edge
+
+    def _gumbel_select(self, entry, env):
+        from .mcts import GUMBEL_DEFAULTS, gumbel_considered_visits
+        score, _ = self._gumbel_scores(entry, env)
+        m_eff = min(int(self.gumbel.get("m", GUMBEL_DEFAULTS["m"])), len(entry.moves))
+        t = int(gumbel_considered_visits(m_eff, self.simulation_num_per_move - 1)[self._cur_sim - 1])
+        eligible = entry.n == t
+        if not eligible.any():                              # a root visit off the schedule (a line back into the root position)
+            eligible = np.ones(len(entry.moves), dtype=bool)
+            self.gumbel_fallbacks += 1
+        edge = self._gumbel_best(score, eligible)
+        return edge, entry.moves[edge]
+
+    def _gumbel_move(self, env):
+        entry = self._table[env.state_key]
+        if entry.moves is None or entry.moves == [-1]:
+            return -1
+        score, _ = self._gumbel_scores(entry, env)
+        return int(entry.moves[self._gumbel_best(score, entry.n == entry.n.max())])
 
     def apply_temperature(self, policy, turn):
         tau = np.power(tau_decay_rate, turn)
@@ -280,6 +348,15 @@ class HivePlayer:
     def calc_policy(self, env):
         """Visit distribution at the root; the priors when every W is negative (solo_play.py:351-374)."""
         entry = self._table[env.state_key]
+        if self.gumbel is not None:
+            # the improved policy over the root's edges; the visit total is unchanged (the pass edge writes nothing)
+            policy, total = np.zeros(ACTION_SPACE), 0
+            if entry.moves is None and len(env.actions()) > 0:
+                entry.open_edges(env.actions())            # a search of one simulation: the root was evaluated, never selected
+            if entry.moves is not None and entry.moves != [-1]:
+                policy[np.asarray(entry.moves)] = self._gumbel_scores(entry, env)[1]
+                total = int(np.sum(entry.n))
+            return policy, total
         visits = np.zeros(ACTION_SPACE)
         priors = np.zeros(ACTION_SPACE)
         if entry.moves is not None:

@@ -214,6 +214,61 @@ int hive_search_policy_where(HiveSearch *s, const int8_t *which, float *policy, 
 /* The clocks, copied into device int32[games]. */
 int hive_search_clocks(HiveSearch *s, int32_t *clock);
 
+/* ---- Gumbel root with sequential halving ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022; the
+ * schedule follows the published mctx implementation).  Opt-in, PUCT mode, ROOT ONLY: below the root the descent is the PUCT
+ * of hive_search_select without noise (the paper's root-only variant; non-root Gumbel selection is not built).
+ *
+ * The rule.  A root has edges e = 0 .. ne-1 in ascending action id with visits N_e, value sums W_e and priors P_e
+ * (renormalised over the legal moves); v_root is the network's value of the root position.
+ *   logit_e = logf(max(P_e, 1e-30f))
+ *   g_e     = 0 for a quiet game (hive_search_set_budgets), else -logf(-logf(u_e)), u_e = the first uniform of the search's
+ *             counter-based generator keyed (seed ^ 0x6A09E667F3BCC909, game id, root turn, simulation 0, slot 0, edge e):
+ *             one draw per edge and search, a pure function of its keys like every other draw here
+ *   q_e     = W_e / N_e where N_e > 0;  SN = sum of N_e
+ *   v_mix   = v_root if SN == 0, else (v_root + SN * (sum over N_b > 0 of P_b q_b) / (sum over N_b > 0 of P_b)) / (1 + SN)
+ *             (v_root too when that sum of priors is 0: the pass edge)
+ *   qc_e    = q_e if N_e > 0 else v_mix;  lo, hi = min, max of qc;  qn_e = (qc_e - lo) / max(hi - lo, 1e-8)
+ *   sigma_e = (c_visit + max_b N_b) * c_scale * qn_e
+ *   score_e = (g_e + logit_e) + sigma_e        fp32, no contraction; the sums / min / max are wave reductions, not bit-pinned
+ * Schedule: considered_visits(m, n) is the sequential-halving sequence of m considered actions and n simulations -- m <= 1:
+ * 0, 1, .., n-1; else with L = ceil(log2 m) and k = m: emit max(1, n / (L k)) times the visit counts of the first k slots,
+ * incrementing them after each emission, then k = max(2, k / 2), until n entries exist.
+ * Selection at the root in simulation s >= 1 (simulation 0 only evaluates the root): t = considered_visits(min(max_considered,
+ * ne), b - 1)[s - 1] with b = budget[g] when budgets are set, else `sims`; the edge is the argmax of score over the edges with
+ * N_e == t, ties to the lower edge; over all edges when none has that count (a root visit taken back because the pool ran out;
+ * counted by hive_search_gumbel_fallbacks).  s is the host's simulation counter, or clock + slot with per-game clocks.  No
+ * Dirichlet noise is drawn for a Gumbel game.
+ * Answer (hive_search_policy / _policy_where): action = argmax of score over the edges with N_e == max_b N_b (all edges before
+ * the first visit), policy[act_e] = softmax_e(logit_e + sigma_e) over all ne edges, sum_n as ever; the pass edge answers -1
+ * and writes nothing.  The "every W negative -> priors" fallback and the selfplay resampling of turns <= 6 do not apply to a
+ * Gumbel game: the Gumbel draw is the exploration, and a quiet game is deterministic.
+ *
+ * c_visit = 50 and c_scale = 1 are the paper's values; they have not been tuned for this game. */
+typedef struct HiveGumbelParams {
+    int32_t max_considered; /* m: root actions sampled without replacement by Gumbel-top-m (16) */
+    float c_visit;          /* 50 */
+    float c_scale;          /* 1.0 */
+    int32_t sims;           /* simulations per search while no budgets are set (the n + 1 of the schedule) */
+} HiveGumbelParams;
+
+/* prm == NULL (the default) switches the Gumbel root off.  where = DEVICE int8[games] the caller owns and the handle keeps the
+ * pointer of, or NULL for every game: a game with where[g] == 0 is searched and answered exactly as without this call, bit for
+ * bit.  Refused with HIVE_E_ARG: UCT mode (here, and hive_search_set_params to UCT while on); a handle with slots > 1 --
+ * visits in flight would desynchronise the schedule; and hive_search_advance_roots returns HIVE_E_ARG while on -- a carried
+ * root has no network value of its own and no fresh schedule. */
+int hive_search_set_gumbel(HiveSearch *s, const HiveGumbelParams *prm, const int8_t *where);
+
+/* The device's schedule function for tests: out_dev[i] = considered_visits(m, n)[i], i = 0 .. n-1 (device int32[n]). */
+int hive_search_gumbel_schedule(int m, int n, int32_t *out_dev, void *stream);
+
+/* The root quantities as the kernels compute them now, for tests and tools: g / logit / qhat (completed q) / improved =
+ * float[games][HIVE_EDGE_CAP] each in edge order (any may be NULL), zero past the last edge and for a game without a tree.
+ * HIVE_E_ARG while the Gumbel root is off. */
+int hive_search_root_gumbel(HiveSearch *s, float *g, float *logit, float *qhat, float *improved);
+
+/* int32[games]: root selections since create that found no edge at the scheduled visit count and took the best of all. */
+int hive_search_gumbel_fallbacks(HiveSearch *s, int32_t *count);
+
 /* The search's own noise generator, exposed for statistical tests: draw d (= 0 .. draws-1) is what the root of game id
  * `first_game + d` would get at (turn, sim 0, slot 0): eta ~ Dirichlet(alpha) over k <= HIVE_EDGE_CAP edges
  * (solo_play.py:322-323, np.random.dirichlet).  out = float[draws][k]; prior = float[k] or NULL:

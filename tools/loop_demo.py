@@ -28,6 +28,7 @@ ap.add_argument("--gate", type=int, default=0, metavar="PAIRS", help="arena pair
 ap.add_argument("--replay", type=int, default=0, metavar="ROWS", help="train from a replay window of ROWS rows shared by the rounds (0 = off)")
 ap.add_argument("--playout-cap", default=None, metavar="FULL,FAST,P", help="full / fast simulations and the share of full plies, e.g. 16,4,0.25")
 ap.add_argument("--rolling", action="store_true", help="every game moves when its own search is done (same games, fewer rounds under a playout cap)")
+ap.add_argument("--gumbel", action="store_true", help="Gumbel root with sequential halving; the records hold the improved policy")
 opts = ap.parse_args()
 gate, window = opts.gate, opts.replay
 cap = None
@@ -46,7 +47,8 @@ trainer = Trainer(net)
 for rnd in range(rounds):
     net.eval()
     sp = mcts.SelfPlay(games, sims, evaluator, seed=100 + rnd, game_ids=range(rnd * games, (rnd + 1) * games),
-                       packed_records=True, max_finished_kept=2 * games, playout_cap=cap, rolling=opts.rolling or None)
+                       packed_records=True, max_finished_kept=2 * games, playout_cap=cap, rolling=opts.rolling or None,
+                       search_options={"gumbel": True} if opts.gumbel else None)
     t0 = time.perf_counter()
     batches = []
     while sp.running() and sp.plies < (80 * sims if opts.rolling else 80):      # (rolling: plies counts turn-overs)
