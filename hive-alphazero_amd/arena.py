@@ -142,11 +142,13 @@ class Arena:
     each side cost.  The first use: how much stronger is one network with 50 simulations than with 10.
 
     gumbel_a / gumbel_b (None | True | {"m", "c_visit", "c_scale"}): that side searches with the Gumbel root and plays
-    argmax(g + logit + sigma(q)) (mcts.ArenaSearch); the other side's searches are untouched."""
+    argmax(g + logit + sigma(q)) (mcts.ArenaSearch); the other side's searches are untouched.
+    gumbel_interior_a / gumbel_interior_b: that side's Gumbel searches also use the Gumbel rule below the root; it needs
+    the side's gumbel_*.  gumbel_a=True, gumbel_b=True, gumbel_interior_a=True: full Gumbel against root-only Gumbel."""
 
     def __init__(self, evaluator_a, evaluator_b, pairs=512, sims=50, slots=1, games_in_flight=1024, seed=0, opening_turns=4,
                  noise_eps=0.0, pair_ids=None, keep_moves=True, device=None, search_options=None, sims_b=None,
-                 gumbel_a=None, gumbel_b=None):
+                 gumbel_a=None, gumbel_b=None, gumbel_interior_a=False, gumbel_interior_b=False):
         import torch
         from . import mcts
         from .batch import BoardBatch
@@ -167,7 +169,9 @@ class Arena:
         self.pair_id = torch.zeros((G,), dtype=torch.int64, device=dev)
         rounds = sims if self.sims_b is None else max(sims, self.sims_b)
         self.search = mcts.ArenaSearch(G, rounds, evaluator_a, evaluator_b, self.a_white, dev.index, slots, seed,
-                                       noise_eps=noise_eps, gumbel_a=gumbel_a, gumbel_b=gumbel_b, **(search_options or {}))
+                                       noise_eps=noise_eps, gumbel_a=gumbel_a, gumbel_b=gumbel_b,
+                                       gumbel_interior_a=gumbel_interior_a, gumbel_interior_b=gumbel_interior_b,
+                                       **(search_options or {}))
         self.budget = torch.zeros((G,), dtype=torch.int32, device=dev) if self.sims_b is not None else None
         self._assign()
         self.result_codes = torch.zeros((G,), dtype=torch.int8, device=dev)

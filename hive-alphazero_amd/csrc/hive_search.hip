@@ -28,6 +28,7 @@ struct SearchDev {
     int32_t *node_nedge, *node_sum_n;
     int8_t *node_term;
     float *node_tv;
+    float *node_v;                                 // [G][MN] value the node was created with: the network's (side to move), or tv
     int16_t *e_act;
     float *e_p, *e_w;
     int32_t *e_n, *e_child;
@@ -55,6 +56,8 @@ struct SearchDev {
     HiveGumbelParams gum;
     const int8_t *gum_where;                       // ... for the games with gum_where[g] != 0 (nullptr: for every game)
     int32_t *gum_fallback;                         // [G] root selections that found no edge at the scheduled visit count
+    int gum_int_on;                                // hive_search_set_gumbel_interior: Gumbel games descend by the interior rule ...
+    const int8_t *gum_int_where;                   // ... where gum_int_where[g] != 0 (nullptr: every Gumbel game)
 };
 
 // the node arrays of one pool: hive_search_advance_roots moves the kept subtrees from the handle's pool into a second one
@@ -64,6 +67,7 @@ struct NodePool {
     int32_t *node_nedge, *node_sum_n;
     int8_t *node_term;
     float *node_tv;
+    float *node_v;
     int16_t *e_act;
     float *e_p, *e_w;
     int32_t *e_n, *e_child;
@@ -184,12 +188,19 @@ __device__ __forceinline__ float gumbel_score(float g, float logit, float sigma)
     const float a = g + logit;
     return a + sigma;
 }
+// below the root: how far the edge's visit share lags the improved policy (hive_search_set_gumbel_interior)
+__device__ __forceinline__ float gumbel_interior_score(float improved, int n, int sum_n)
+{
+#pragma clang fp contract(off)
+    return improved - (float)n / (1.0f + (float)sum_n);
+}
 
-// The per-edge quantities of a Gumbel root, edge e = lane + 64 k in slot k: g, logit, completed q, sigma and the visits.
-// nv[k] = -1 marks a slot past the last edge.  max_n / sum_n are wave-uniform.
-__device__ __forceinline__ void wave_gumbel_root(const SearchDev &S, int g, long long eb, int ne, unsigned root_turn, bool quiet,
-                                                 int lane, float gum[4], float logit[4], float qhat[4], float sigma[4], int nv[4],
-                                                 int &max_n, int &sum_n)
+// The per-edge quantities of a Gumbel node, edge e = lane + 64 k in slot k: g, logit, completed q, sigma and the visits.
+// v_node = the network's value of the node's own position (root_v at the root, node_v below it); draw = the g of a root
+// that is not quiet, else g = 0.  nv[k] = -1 marks a slot past the last edge.  max_n / sum_n are wave-uniform.
+__device__ __forceinline__ void wave_gumbel_root(const SearchDev &S, int g, long long eb, int ne, unsigned root_turn, float v_node,
+                                                 bool draw, int lane, float gum[4], float logit[4], float qhat[4], float sigma[4],
+                                                 int nv[4], int &max_n, int &sum_n)
 {
     int nsum = 0, nmax = 0;
     float pq = 0.f, pv = 0.f;
@@ -202,7 +213,7 @@ __device__ __forceinline__ void wave_gumbel_root(const SearchDev &S, int g, long
             const int n = S.e_n[eb + e];
             nv[k] = n;
             logit[k] = logf(fmaxf(p, 1e-30f));
-            if (!quiet) {
+            if (draw) {
                 Rng r = noise_rng(S.seed ^ kGumbelStream, S.game_id[g], root_turn, 0ull, 0, e);
                 gum[k] = -logf(-logf(r.uniform()));
             }
@@ -219,9 +230,8 @@ __device__ __forceinline__ void wave_gumbel_root(const SearchDev &S, int g, long
     for (int o = 32; o > 0; o >>= 1) { const int x = __shfl_xor(nmax, o); nmax = x > nmax ? x : nmax; }
     pq = wave_sum(pq);
     pv = wave_sum(pv);
-    const float v_root = S.root_v[g];
-    // (visited edges whose priors are all zero -- the pass edge -- leave the mixed value at the root's)
-    const float v_mix = (nsum == 0 || !(pv > 0.f)) ? v_root : (v_root + (float)nsum * (pq / pv)) / (1.0f + (float)nsum);
+    // (visited edges whose priors are all zero -- the pass edge -- leave the mixed value at the node's own)
+    const float v_mix = (nsum == 0 || !(pv > 0.f)) ? v_node : (v_node + (float)nsum * (pq / pv)) / (1.0f + (float)nsum);
     float lo = 3.0e38f, hi = -3.0e38f;
     for (int k = 0; k < 4; ++k)
         if (nv[k] >= 0) {
@@ -367,6 +377,7 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
     const unsigned root_turn = reinterpret_cast<const uint8_t *>(st)[33];
     const bool quiet = S.quiet != nullptr && S.quiet[g] != 0;
     const bool gumbel = gumbel_game(S, g);
+    const bool interior = gumbel && S.gum_int_on && (S.gum_int_where == nullptr || S.gum_int_where[g] != 0);
     while (true) {
         if (S.node_term[nbase + node]) { kind = LEAF_TERMINAL; leafnode = node; break; }          // game over (solo_play.py:169-180)
         if ((int)reinterpret_cast<const uint8_t *>(st)[33] >= S.prm.max_game_length) { kind = LEAF_CAPDRAW; break; }   // :181-183
@@ -385,10 +396,11 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
         int bidx = 0x7FFFFFFF;
         if (depth == 0 && gumbel) {
             // Gumbel root: simulation s >= 1 goes to the best-scoring edge among those that hold the visit count the
-            // sequential-halving schedule asks for; below the root the descent is the PUCT of the loop below, without noise
+            // sequential-halving schedule asks for; below the root the descent is the PUCT of the loop below, without noise,
+            // or the interior rule (hive_search_set_gumbel_interior)
             float gum[4], logit[4], qhat[4], sigma[4];
             int nv[4], max_n, sum_n;
-            wave_gumbel_root(S, g, eb, ne, root_turn, quiet, lane, gum, logit, qhat, sigma, nv, max_n, sum_n);
+            wave_gumbel_root(S, g, eb, ne, root_turn, S.root_v[g], !quiet, lane, gum, logit, qhat, sigma, nv, max_n, sum_n);
             const int n_sched = (S.budget != nullptr ? S.budget[g] : S.gum.sims) - 1;
             const int m_eff = S.gum.max_considered < ne ? S.gum.max_considered : ne;
             const int t = gumbel_considered_visit(m_eff, n_sched, (int)sim - 1);
@@ -407,6 +419,25 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
                 if (lane == 0) S.gum_fallback[g] += 1;
             }
             if (bidx >= ne) bidx = 0;                        // (scores that are not numbers compare false everywhere)
+        } else if (interior) {
+            // Gumbel below the root: the edge whose visit share lags softmax(logit + sigma(completed q)) most; no noise, no
+            // c_puct.  One slot only, so N holds no visit in flight but this descent's own (a line back into a node).
+            bidx = 0;                                        // a single edge (the pass edge: P = 0) is taken as it is
+            if (ne > 1) {
+                float gum[4], logit[4], qhat[4], sigma[4], improved[4];
+                int nv[4], max_n, sum_n;
+                wave_gumbel_root(S, g, eb, ne, root_turn, S.node_v[nbase + node], false, lane, gum, logit, qhat, sigma, nv, max_n,
+                                 sum_n);
+                wave_gumbel_improved(logit, sigma, nv, improved);
+                bidx = 0x7FFFFFFF;
+                for (int k = 0; k < 4; ++k)
+                    if (nv[k] >= 0) {
+                        const float b = gumbel_interior_score(improved[k], nv[k], sum_n);
+                        if (b > best) { best = b; bidx = lane + 64 * k; }
+                    }
+                wave_argmax(best, bidx);
+                if (bidx >= ne) bidx = 0;                    // (scores that are not numbers compare false everywhere)
+            }
         } else {
             for (int k = 0; k < 4; ++k) {
                 int e = lane + 64 * k;
@@ -589,6 +620,7 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
             S.node_sum_n[nbase + id] = 0;
             S.node_term[nbase + id] = term ? 1 : 0;
             S.node_tv[nbase + id] = tv;
+            S.node_v[nbase + id] = term ? tv : v[g];            // the interior Gumbel rule completes unvisited edges with it
             S.n_nodes[g] = id + 1;
             if (kind == LEAF_EXPAND) S.e_child[(nbase + S.leaf_node[sg]) * EC + S.leaf_edge[sg]] = id;
         }
@@ -642,7 +674,8 @@ search_policy_kernel(SearchDev S, const int8_t *__restrict__ which, float *__res
         const bool quiet = S.quiet != nullptr && S.quiet[g] != 0;
         float gum[4], logit[4], qhat[4], sigma[4], improved[4];
         int nv[4], max_n, visits;
-        wave_gumbel_root(S, g, eb, ne, S.node_board[nbase].turn, quiet, lane, gum, logit, qhat, sigma, nv, max_n, visits);
+        wave_gumbel_root(S, g, eb, ne, S.node_board[nbase].turn, S.root_v[g], !quiet, lane, gum, logit, qhat, sigma, nv, max_n,
+                         visits);
         wave_gumbel_improved(logit, sigma, nv, improved);
         float best = -3.0e38f;
         int bidx = 0x7FFFFFFF;
@@ -824,7 +857,8 @@ search_root_gumbel_kernel(SearchDev S, float *__restrict__ gum_out, float *__res
     int nv[4] = {-1, -1, -1, -1}, max_n, visits;
     if (tree) {
         const bool quiet = S.quiet != nullptr && S.quiet[g] != 0;
-        wave_gumbel_root(S, g, eb, ne, S.node_board[nbase].turn, quiet, lane, gum, logit, qhat, sigma, nv, max_n, visits);
+        wave_gumbel_root(S, g, eb, ne, S.node_board[nbase].turn, S.root_v[g], !quiet, lane, gum, logit, qhat, sigma, nv, max_n,
+                         visits);
         wave_gumbel_improved(logit, sigma, nv, improved);
     }
     for (int k = 0; k < 4; ++k) {
@@ -982,6 +1016,7 @@ search_advance_kernel(SearchDev S, NodePool D, const int32_t *__restrict__ playe
             D.node_sum_n[dn] = S.node_sum_n[so];
             D.node_term[dn] = S.node_term[so];
             D.node_tv[dn] = S.node_tv[so];
+            D.node_v[dn] = S.node_v[so];
         }
         for (int e = lane; e < ne; e += 64) {
             D.e_act[dn * EC + e] = S.e_act[so * EC + e];
@@ -1058,6 +1093,7 @@ static int search_alloc(HiveSearch *s, int games, int max_nodes, int slots)
     S_TRY(alloc(s, &d.node_sum_n, GN));
     S_TRY(alloc(s, &d.node_term, GN));
     S_TRY(alloc(s, &d.node_tv, GN));
+    S_TRY(alloc(s, &d.node_v, GN));
     S_TRY(alloc(s, &d.e_act, GE));
     S_TRY(alloc(s, &d.e_p, GE));
     S_TRY(alloc(s, &d.e_w, GE));
@@ -1108,6 +1144,7 @@ static int search_alloc(HiveSearch *s, int games, int max_nodes, int slots)
     S_TRY(hipMemset(d.leaf_kind, 0, LG));
     S_TRY(hipMemset(d.path_len, 0, sizeof(int32_t) * LG));
     S_TRY(hipMemset(d.node_term, 0, GN));
+    S_TRY(hipMemset(d.node_v, 0, sizeof(float) * GN));
     return HIVE_OK;
 }
 
@@ -1256,6 +1293,24 @@ int hive_search_set_gumbel(HiveSearch *s, const HiveGumbelParams *prm, const int
     return HIVE_OK;
 }
 
+int hive_search_set_gumbel_interior(HiveSearch *s, int on, const int8_t *where)
+{
+    if (!s) return hive::set_error(HIVE_E_ARG, "null handle");
+    // read by Gumbel games alone (gumbel_game): accepted before or after hive_search_set_gumbel, in any mode
+    s->d.gum_int_on = on ? 1 : 0;
+    s->d.gum_int_where = on ? where : nullptr;
+    return HIVE_OK;
+}
+
+int hive_search_node_values(HiveSearch *s, int game, float *node_v)
+{
+    if (!s || !node_v || game < 0 || game >= s->d.G) return hive::set_error(HIVE_E_ARG, "hive_search_node_values: bad argument");
+    S_TRY(hipSetDevice(s->device));
+    S_TRY(hipMemcpyAsync(node_v, s->d.node_v + (size_t)game * s->d.MN, sizeof(float) * (size_t)s->d.MN, hipMemcpyDeviceToDevice,
+                         s->stream));
+    return HIVE_OK;
+}
+
 int hive_search_gumbel_schedule(int m, int n, int32_t *out_dev, void *stream)
 {
     if (m < 1 || n < 1 || !out_dev) return hive::set_error(HIVE_E_ARG, "hive_search_gumbel_schedule: bad argument");
@@ -1328,24 +1383,26 @@ int hive_search_advance_roots(HiveSearch *s, const int32_t *played, const HiveBo
         S_TRY(alloc(s, &a.node_sum_n, GN));
         S_TRY(alloc(s, &a.node_term, GN));
         S_TRY(alloc(s, &a.node_tv, GN));
+        S_TRY(alloc(s, &a.node_v, GN));
         S_TRY(alloc(s, &a.e_act, GE));
         S_TRY(alloc(s, &a.e_p, GE));
         S_TRY(alloc(s, &a.e_w, GE));
         S_TRY(alloc(s, &a.e_n, GE));
         S_TRY(alloc(s, &a.e_child, GE));
         S_TRY(hipMemset(a.node_term, 0, GN));
+        S_TRY(hipMemset(a.node_v, 0, sizeof(float) * GN));
         s->have_alt = true;
     }
     hipLaunchKernelGGL(search_advance_kernel, dim3((unsigned)((d.G + waves - 1) / waves)), dim3(64 * waves), waves * per_wave,
                        s->stream, d, s->alt, played, boards, hist, active);
     S_TRY(hipGetLastError());
     // every later launch (stream order) works on the pool the kernel wrote
-    const NodePool old{d.node_board, d.node_hist, d.node_nedge, d.node_sum_n, d.node_term, d.node_tv,
+    const NodePool old{d.node_board, d.node_hist, d.node_nedge, d.node_sum_n, d.node_term, d.node_tv, d.node_v,
                        d.e_act, d.e_p, d.e_w, d.e_n, d.e_child};
     const NodePool &a = s->alt;
     d.node_board = a.node_board; d.node_hist = a.node_hist; d.node_nedge = a.node_nedge; d.node_sum_n = a.node_sum_n;
-    d.node_term = a.node_term; d.node_tv = a.node_tv; d.e_act = a.e_act; d.e_p = a.e_p; d.e_w = a.e_w; d.e_n = a.e_n;
-    d.e_child = a.e_child;
+    d.node_term = a.node_term; d.node_tv = a.node_tv; d.node_v = a.node_v; d.e_act = a.e_act; d.e_p = a.e_p; d.e_w = a.e_w;
+    d.e_n = a.e_n; d.e_child = a.e_child;
     s->alt = old;
     s->sim = 0;
     return HIVE_OK;

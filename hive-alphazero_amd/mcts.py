@@ -181,6 +181,27 @@ def gumbel_options(gumbel, slots=1, mode=PUCT, keep_tree=False):
     return opt
 
 
+def gumbel_interior_options(gumbel_interior, gumbel):
+    """TreeSearch's `gumbel_interior` argument checked (no GPU): True iff the Gumbel rule also selects below the root.  It is an
+    option of the Gumbel root, not a search of its own: without `gumbel` it is refused."""
+    if gumbel_interior and not gumbel:
+        raise ValueError("gumbel_interior: needs the Gumbel root (gumbel=True or its option dict)")
+    return bool(gumbel_interior)
+
+
+def gumbel_interior_choice(p, n, w, v_node, c_visit=GUMBEL_DEFAULTS["c_visit"], c_scale=GUMBEL_DEFAULTS["c_scale"]):
+    """(edge, score float64[ne]) of the Gumbel rule below the root at a node with priors p, visits n, value sums w and the value
+    v_node its position was predicted with (include/hive_search.h, hive_search_set_gumbel_interior), in float64:
+    score = improved policy - n / (1 + sum n); the edge is the first maximum.  A single edge is taken as it is."""
+    import numpy as np
+    n = np.asarray(n, dtype=np.int64)
+    if n.size == 1:
+        return 0, np.zeros(1)
+    _, improved = gumbel_improved_policy(p, n, w, v_node, c_visit, c_scale)
+    score = improved - n / (1.0 + float(n.sum()))
+    return int(np.argmax(score)), score
+
+
 class _GumbelParams(ctypes.Structure):
     _fields_ = [("max_considered", ctypes.c_int32), ("c_visit", ctypes.c_float), ("c_scale", ctypes.c_float),
                 ("sims", ctypes.c_int32)]
@@ -199,7 +220,7 @@ class TreeSearch:
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  c_puct=0.7, noise_eps=0.25, dirichlet_alpha=0.3, max_nodes=None, transpositions=True, mode=PUCT,
                  virtual_loss=None, max_game_length=None, skip_unread_rows=True, share_equal_leaves=True, reuse_store=0,
-                 keep_tree=False, rolling=False, gumbel=None):
+                 keep_tree=False, rolling=False, gumbel=None, gumbel_interior=False):
         """mode = PUCT: woker/solo_play.py::HivePlayer; mode = UCT: alpha_zero/MCTS_chess.py::UCT_search (plain tree, no
         noise, no length cap; with one slot the virtual loss is 0 so that W sums exactly like the sequential reference).
 
@@ -220,8 +241,15 @@ class TreeSearch:
         softmax(logit + sigma(completed q)), dense over the legal moves, instead of the visit histogram.  Below the root the
         search is unchanged.  Works with budgets, quiet (g = 0: deterministic) and rolling; refused with slots > 1, UCT and
         keep_tree (gumbel_options).  c_visit / c_scale are the paper's values and have not been tuned here.
-        set_gumbel_where(mask) restricts it to some games; the others are searched as without it, bit for bit."""
+        set_gumbel_where(mask) restricts it to some games; the others are searched as without it, bit for bit.
+
+        gumbel_interior = True (needs gumbel): the Gumbel rule also selects below the root
+        (hive_search_set_gumbel_interior): at every deeper node the descent takes the edge whose visit share lags
+        softmax(logit + sigma(completed q)) most, unvisited children completed by the node's mixed value, in place of PUCT.
+        Deterministic, no c_puct; the root's schedule and answer are unchanged.  set_gumbel_interior(on, where) switches it
+        and restricts it to some of the Gumbel games."""
         gumbel = gumbel_options(gumbel, slots, mode, keep_tree)
+        gumbel_interior = gumbel_interior_options(gumbel_interior, gumbel)
         if rolling and keep_tree:
             raise ValueError("TreeSearch: rolling cannot keep trees (hive_search_advance_roots moves every tree at once)")
         L = load()
@@ -262,6 +290,9 @@ class TreeSearch:
         self.gumbel = self._gumbel_where = self._gumbel_sims = None
         if gumbel is not None:
             self.set_gumbel(gumbel)
+        self.gumbel_interior, self._gumbel_interior_where = False, None
+        if gumbel_interior:
+            self.set_gumbel_interior(True)
         n = games * slots
         dev = self.device
         self.plane_dtype = plane_dtype
@@ -416,6 +447,29 @@ class TreeSearch:
         if self.gumbel is None:
             raise ValueError("TreeSearch.set_gumbel_where: the Gumbel root is off (gumbel=... / set_gumbel)")
         self.set_gumbel(self.gumbel, mask)
+
+    def set_gumbel_interior(self, on=True, where=None):
+        """The Gumbel rule below the root on or off, for the Gumbel games with where[g] != 0 (int8 / bool [games]; None =
+        every Gumbel game): hive_search_set_gumbel_interior.  It acts on Gumbel games only and survives set_gumbel(None) /
+        set_gumbel(...): switching the Gumbel root off and on leaves it as it was."""
+        if on and where is not None:
+            where = torch.as_tensor(where).to(device=self.device, dtype=torch.int8).contiguous()
+            assert where.numel() == self.games
+        else:
+            where = None
+        check(self.L.hive_search_set_gumbel_interior(self._h, 1 if on else 0, _p(where)))
+        # (the handle keeps the address of `where`: this object keeps the tensor)
+        self.gumbel_interior, self._gumbel_interior_where = bool(on), where
+
+    def node_values(self, game):
+        """float32[n]: the value every node of game `game`'s tree was created with, in export_tree's node order
+        (hive_search_node_values)."""
+        out = torch.zeros((self.max_nodes,), dtype=torch.float32, device=self.device)
+        count = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._stream()
+        check(self.L.hive_search_node_values(self._h, int(game), _p(out)))
+        check(self.L.hive_search_export_tree(self._h, int(game), _p(count), *([None] * 11)))
+        return out[:int(count.item())].cpu().numpy()
 
     def root_gumbel(self):
         """(g, logit, completed q, improved policy) fp32[games,256] of the roots as they stand, in edge order (ascending
@@ -630,10 +684,13 @@ class ArenaSearch(TreeSearch):
 
     gumbel_a / gumbel_b (None | True | dict, as TreeSearch's gumbel): the side searches with the Gumbel root.  At every search
     game g is a Gumbel game iff the owner of its search -- the rule above -- has the option; the other side's games are
-    searched as without it, bit for bit.  One handle holds one parameter set: two dicts must be equal."""
+    searched as without it, bit for bit.  One handle holds one parameter set: two dicts must be equal.
+    gumbel_interior_a / gumbel_interior_b: that side's Gumbel searches also select below the root by the Gumbel rule
+    (TreeSearch, gumbel_interior); a side with it must have gumbel_*.  gumbel_a=True, gumbel_b=True, gumbel_interior_a=True
+    is full Gumbel against root-only Gumbel on one handle."""
 
     def __init__(self, games, sims, evaluator_a, evaluator_b, a_white, device=None, slots=1, seed=0, plane_dtype=None,
-                 gumbel_a=None, gumbel_b=None, **options):
+                 gumbel_a=None, gumbel_b=None, gumbel_interior_a=False, gumbel_interior_b=False, **options):
         if options.get("reuse_store"):
             raise ValueError("ArenaSearch: reuse_store keeps evaluations by position alone, not by network")
         if options.get("keep_tree"):
@@ -642,14 +699,22 @@ class ArenaSearch(TreeSearch):
             raise ValueError("ArenaSearch: rolling is not built for the arena (both sides' searches run in lock step)")
         if options.get("gumbel"):
             raise ValueError("ArenaSearch: give the Gumbel root per side, gumbel_a / gumbel_b")
+        if options.get("gumbel_interior"):
+            raise ValueError("ArenaSearch: give the interior rule per side, gumbel_interior_a / gumbel_interior_b")
         sides = [gumbel_options(x, slots, options.get("mode", PUCT)) for x in (gumbel_a, gumbel_b)]
         if sides[0] is not None and sides[1] is not None and sides[0] != sides[1]:
             raise ValueError("ArenaSearch: one handle holds one Gumbel parameter set; gumbel_a and gumbel_b differ")
+        interior = (gumbel_interior_options(gumbel_interior_a, sides[0]), gumbel_interior_options(gumbel_interior_b, sides[1]))
         super().__init__(games, sims, evaluator_a, device, slots, seed, plane_dtype,
                          **dict(options, gumbel=sides[0] or sides[1]))
         self._gumbel_sides = (sides[0] is not None, sides[1] is not None)
         if self._gumbel_sides[0] != self._gumbel_sides[1]:      # one side only: the mask is rewritten in place at every search
             self.set_gumbel_where(torch.zeros((games,), dtype=torch.int8, device=self.device))
+        self._interior_sides = interior
+        if interior[0] != interior[1]:                          # likewise: rewritten in place from the ownership rule
+            self.set_gumbel_interior(True, torch.zeros((games,), dtype=torch.int8, device=self.device))
+        elif interior[0]:
+            self.set_gumbel_interior(True)
         self.evaluator_a, self.evaluator_b = evaluator_a, evaluator_b
         assert a_white.dtype == torch.int8 and a_white.numel() == games and a_white.is_cuda and a_white.is_contiguous()
         self.a_white = a_white
@@ -674,10 +739,13 @@ class ArenaSearch(TreeSearch):
 
     def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False, budgets=None, quiet=None):
         self._roots = root_boards
-        if self._gumbel_where is not None:
+        if self._gumbel_where is not None or self._gumbel_interior_where is not None:
             # the owner of the search of game g (hive_arena_budget_launch's rule): A iff a_white[g] == (root turn is odd)
             a_owns = (self.a_white != 0) == ((root_boards[:, 33] & 1) != 0)
-            self._gumbel_where.copy_(a_owns if self._gumbel_sides[0] else ~a_owns)
+            if self._gumbel_where is not None:
+                self._gumbel_where.copy_(a_owns if self._gumbel_sides[0] else ~a_owns)
+            if self._gumbel_interior_where is not None:
+                self._gumbel_interior_where.copy_(a_owns if self._interior_sides[0] else ~a_owns)
         out = super().search(root_boards, root_hist, active, selfplay, keep_root_planes, budgets=budgets, quiet=quiet)
         torch.sum(self.rows, 0, keepdim=True, out=self.evals_run)
         return out
@@ -750,7 +818,8 @@ class SelfPlay:
     search_options = {"gumbel": True | {"m", "c_visit", "c_scale"}}: every search uses the Gumbel root (TreeSearch, gumbel).  The
     move is the root's argmax(g + logit + sigma(q)) -- the opening resampling of turns <= 6 does not apply, the Gumbel draw is
     the exploration -- and the recorded policy is the improved policy, through the same record route.  In lock step, with
-    playout_cap (a quiet fast ply has g = 0 and is deterministic) and with rolling; one slot, no keep_tree."""
+    playout_cap (a quiet fast ply has g = 0 and is deterministic) and with rolling; one slot, no keep_tree.
+    {"gumbel": True, "gumbel_interior": True} adds the Gumbel rule below the root (TreeSearch, gumbel_interior)."""
 
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  keep_records=True, game_ids=None, max_finished_kept=1024, report_every=0, log=print, packed_records=False,

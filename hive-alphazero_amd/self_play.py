@@ -151,7 +151,8 @@ class SelfPlayWorker:
     `sims` = max(full, fast); every game moving when its own search is done).  Both need row_format="compact": the packed
     hand-over carries the `full` key of a capped batch, the reference's JSON rows have no room for it, and a rolling child
     hands over games one by one as they end.  search_options (e.g. {"gumbel": True}: the Gumbel root of mcts.TreeSearch) go
-    to every child's SelfPlay(search_options=...) unchanged."""
+    to every child's SelfPlay(search_options=...) unchanged; {"gumbel": True, "gumbel_interior": True} adds the Gumbel rule
+    below the root."""
 
     def __init__(self, total_games, games_per_gpu=1024, sims=50, gpus=None, seed=0, net_seed=0, checkpoint=None, slots=1,
                  datapath="../dataSelf", games_per_file=100, report_every=10, worker=_game_worker, log=print, row_format="json",
@@ -178,7 +179,9 @@ class SelfPlayWorker:
         if search_options:
             # refused here, before any child starts, as every child's SelfPlay would refuse it
             from . import mcts
-            mcts.gumbel_options(search_options.get("gumbel"), int(slots), keep_tree=bool(search_options.get("keep_tree")))
+            mcts.gumbel_interior_options(
+                search_options.get("gumbel_interior"),
+                mcts.gumbel_options(search_options.get("gumbel"), int(slots), keep_tree=bool(search_options.get("keep_tree"))))
             mcts.rolling_options(self.cfg["rolling"], search_options, int(sims), int(slots), self.cfg["playout_cap"])
         if gpus is None:
             import torch

@@ -41,10 +41,11 @@ _DRAW = 5          # sentinel a drawn / length-capped line returns (solo_play.py
 class _Entry:
     """One position of the transposition table: raw network priors until its first selection, then
     per-edge arrays in legal-move order."""
-    __slots__ = ("raw_p", "moves", "n", "w", "p", "sum_n")
+    __slots__ = ("raw_p", "moves", "n", "w", "p", "sum_n", "v")
 
-    def __init__(self, raw_p):
+    def __init__(self, raw_p, v=0.0):
         self.raw_p = raw_p
+        self.v = v                     # the value this position was predicted with (the Gumbel rule below the root reads it)
         self.moves = None
         self.n = self.w = self.p = None
         self.sum_n = 0
@@ -172,6 +173,10 @@ class HivePlayer:
     # SEARCH_THREADS = 1 only; not with keep_tree.  After action(): gumbel_fallbacks = selections that found no edge at the
     # scheduled count, gumbel_min_gap = the smallest strictly positive gap between the two best scores over those selections
     # and the final choice (inf if none).
+    # "interior": True -- the Gumbel rule below the root as well (hive_search_set_gumbel_interior): at depth >= 1 the edge is
+    # the first maximum of improved policy - n / (1 + sum n), the improved policy taken with the value the entry's position
+    # was predicted with (mcts.gumbel_interior_choice); no noise, no c_puct.  gumbel_min_gap then covers those selections
+    # too, and gumbel_interior_min_gap holds theirs alone.
     gumbel = None
 
     def action(self, env, non_queue=True):
@@ -186,6 +191,7 @@ class HivePlayer:
                 raise ValueError("HivePlayer.gumbel: sequential search without kept trees only")
             self._sim, self._root_v, self._root_g = 0, 0.0, None
             self.gumbel_fallbacks, self.gumbel_min_gap = 0, float("inf")
+            self.gumbel_interior_min_gap = float("inf")
         self.search_moves(env)
         policy, visits = self.calc_policy(env)
         if self.gumbel is not None:
@@ -220,7 +226,7 @@ class HivePlayer:
                 entry = self._table.get(key)
                 if entry is None:
                     leaf_p, leaf_v = self._evaluate(env)
-                    self._table[key] = _Entry(leaf_p)
+                    self._table[key] = _Entry(leaf_p, float(np.asarray(leaf_v).reshape(-1)[0]))
                     outcome = leaf_v
                     if self.gumbel is not None and is_root_node and depth == 0:
                         self._root_v = float(np.asarray(leaf_v).reshape(-1)[0])      # completes the unvisited root edges
@@ -284,6 +290,8 @@ class HivePlayer:
             entry.open_edges(legal)
         if at_root and self.gumbel is not None:
             return self._gumbel_select(entry, env)
+        if self.gumbel is not None and self.gumbel.get("interior"):
+            return self._gumbel_interior_select(entry)
         prior = entry.p
         if at_root:
             noise = np.random.dirichlet([dirichlet_alpha] * len(entry.moves))
@@ -327,6 +335,20 @@ class HivePlayer:
             eligible = np.ones(len(entry.moves), dtype=bool)
             self.gumbel_fallbacks += 1
         edge = self._gumbel_best(score, eligible)
+        return edge, entry.moves[edge]
+
+    def _gumbel_interior_select(self, entry):
+        """The Gumbel rule below the root: the edge whose visit share lags the improved policy most."""
+        from .mcts import GUMBEL_DEFAULTS, gumbel_interior_choice
+        opt = self.gumbel
+        edge, score = gumbel_interior_choice(entry.p, entry.n, entry.w, entry.v,
+                                             opt.get("c_visit", GUMBEL_DEFAULTS["c_visit"]),
+                                             opt.get("c_scale", GUMBEL_DEFAULTS["c_scale"]))
+        rest = np.delete(score, edge)
+        if rest.size and score[edge] - rest.max() > 0:
+            gap = float(score[edge] - rest.max())
+            self.gumbel_min_gap = min(self.gumbel_min_gap, gap)
+            self.gumbel_interior_min_gap = min(self.gumbel_interior_min_gap, gap)
         return edge, entry.moves[edge]
 
     def _gumbel_move(self, env):

@@ -102,6 +102,13 @@ int hive_search_export_tree(HiveSearch *s, int game, int32_t *n_nodes, HiveBoard
                             int32_t *sum_n, int8_t *term, float *tv, int16_t *e_act, float *e_p, int32_t *e_n, float *e_w,
                             int32_t *e_child);
 
+/* The value every node of one game's tree was created with, for tests and tools: node_v = float[max_nodes], of which only
+ * the first n_nodes entries (hive_search_export_tree) are meaningful.  A node that is not a finished game holds the network's
+ * value of its own position from the side to move there (the v of the hive_search_backup that created it; node 0: the
+ * root's); a finished game or a position at the length cap holds its tv.  Written for every node in every mode;
+ * hive_search_advance_roots moves it with the kept nodes like tv. */
+int hive_search_node_values(HiveSearch *s, int game, float *node_v);
+
 /* Selection for in-flight slot `slot`: leaf_boards / leaf_hist = [games] records of the positions to
  * evaluate (untouched for games whose path ended in a known terminal node or a collision). */
 int hive_search_select(HiveSearch *s, int slot, HiveBoard *leaf_boards, HiveHistory *leaf_hist);
@@ -217,6 +224,8 @@ int hive_search_clocks(HiveSearch *s, int32_t *clock);
 /* ---- Gumbel root with sequential halving ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022; the
  * schedule follows the published mctx implementation).  Opt-in, PUCT mode, ROOT ONLY: below the root the descent is the PUCT
  * of hive_search_select without noise (the paper's root-only variant; non-root Gumbel selection is not built).
+ * hive_search_set_gumbel_interior, further down, lifts that restriction for the games it names: it is a call of its own and
+ * this block describes the search without it.
  *
  * The rule.  A root has edges e = 0 .. ne-1 in ascending action id with visits N_e, value sums W_e and priors P_e
  * (renormalised over the legal moves); v_root is the network's value of the root position.
@@ -268,6 +277,29 @@ int hive_search_root_gumbel(HiveSearch *s, float *g, float *logit, float *qhat, 
 
 /* int32[games]: root selections since create that found no edge at the scheduled visit count and took the best of all. */
 int hive_search_gumbel_fallbacks(HiveSearch *s, int32_t *count);
+
+/* ---- Gumbel selection below the root (section 5 of the same paper; mctx: gumbel_muzero_interior_action_selection).  Opt-in
+ * on top of hive_search_set_gumbel.  Game g uses the rule iff it is a Gumbel game (hive_search_set_gumbel and its `where`),
+ * on != 0 and (where == NULL or where[g] != 0); where = DEVICE int8[games] the caller owns and the handle keeps the pointer
+ * of.  On every other game the call has no effect of any kind, bit for bit.  Accepted before or after
+ * hive_search_set_gumbel; the default is off, and switching the Gumbel root off and on leaves this setting as it was.
+ *
+ * The rule.  It applies at a node x that the descent of such a game reaches at depth d >= 1 -- node 0 too, when a
+ * transposition leads back to it; depth 0 stays the sequential-halving selection above.  x has edges e = 0 .. ne-1 with
+ * P_e, N_e, W_e, and v_x = the value x was created with (hive_search_node_values).  logit_e, q_e, SN, v_mix, qc_e, qn_e and
+ * sigma_e are the root's formulas above with v_x in the place of v_root and x's own max_b N_b.  There is no g_e: no noise is
+ * drawn, for quiet and other games alike, and c_puct is not read.
+ *   pi'_e   = softmax_e(logit_e + sigma_e) over all ne edges (the improved policy of hive_search_policy, at x)
+ *   score_e = pi'_e - (float)N_e / (1.0f + (float)SN)        fp32, no contraction
+ * The edge is the argmax of score, ties to the lower edge: the child whose visit share lags pi' most.  Unvisited children
+ * are completed by v_mix, not by the q = 0 of PUCT.  A node with a single edge takes it as it is (the pass edge has P = 0).
+ * Everything after the choice -- virtual loss, the move, the transposition lookup, expansion, pool exhaustion, the length
+ * cap, finished games -- is hive_search_select's.  Gumbel games run on one slot (slots > 1 is refused by
+ * hive_search_set_gumbel), so N_e holds no visit in flight of another simulation: the only virtual visits x can see are
+ * this descent's own, when its line came through x before.
+ * Unchanged: the answer at the root (action, improved policy, sum_n), hive_search_root_gumbel, budgets, per-game clocks, the
+ * root's `where`, and every refusal of hive_search_set_gumbel. */
+int hive_search_set_gumbel_interior(HiveSearch *s, int on, const int8_t *where);
 
 /* The search's own noise generator, exposed for statistical tests: draw d (= 0 .. draws-1) is what the root of game id
  * `first_game + d` would get at (turn, sim 0, slot 0): eta ~ Dirichlet(alpha) over k <= HIVE_EDGE_CAP edges

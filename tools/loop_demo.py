@@ -17,7 +17,10 @@ FULL simulations with probability P and becomes a training row, else with FAST s
 search then runs max(FULL, FAST) simulations and the trainer sees the rows flagged full (both routes filter them).
 
 --rolling (default off): mcts.SelfPlay(rolling=True) -- every game moves when its own search is done instead of waiting for
-the longest search of the batch; the same games, bit for bit, in fewer rounds when the plies' searches differ in length."""
+the longest search of the batch; the same games, bit for bit, in fewer rounds when the plies' searches differ in length.
+
+--gumbel (default off): the Gumbel root with sequential halving; --gumbel-interior adds the Gumbel rule below the root (it
+requires --gumbel)."""
 import argparse, os, sys, time, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hive_alphazero_amd import mcts, records
@@ -29,7 +32,10 @@ ap.add_argument("--replay", type=int, default=0, metavar="ROWS", help="train fro
 ap.add_argument("--playout-cap", default=None, metavar="FULL,FAST,P", help="full / fast simulations and the share of full plies, e.g. 16,4,0.25")
 ap.add_argument("--rolling", action="store_true", help="every game moves when its own search is done (same games, fewer rounds under a playout cap)")
 ap.add_argument("--gumbel", action="store_true", help="Gumbel root with sequential halving; the records hold the improved policy")
+ap.add_argument("--gumbel-interior", action="store_true", help="with --gumbel: the Gumbel rule also selects below the root")
 opts = ap.parse_args()
+if opts.gumbel_interior and not opts.gumbel:
+    ap.error("--gumbel-interior requires --gumbel")
 gate, window = opts.gate, opts.replay
 cap = None
 if opts.playout_cap:
@@ -48,7 +54,7 @@ for rnd in range(rounds):
     net.eval()
     sp = mcts.SelfPlay(games, sims, evaluator, seed=100 + rnd, game_ids=range(rnd * games, (rnd + 1) * games),
                        packed_records=True, max_finished_kept=2 * games, playout_cap=cap, rolling=opts.rolling or None,
-                       search_options={"gumbel": True} if opts.gumbel else None)
+                       search_options={"gumbel": True, "gumbel_interior": opts.gumbel_interior} if opts.gumbel else None)
     t0 = time.perf_counter()
     batches = []
     while sp.running() and sp.plies < (80 * sims if opts.rolling else 80):      # (rolling: plies counts turn-overs)
