@@ -11,6 +11,7 @@ alpha_zero/alpha_net.py does `mkdir ./datasets/iter3/` in the cwd):
 
     python3 -B oracle/gen_golden.py tables
     python3 -B oracle/gen_golden.py games   --games 64 --procs 8
+    python3 -B oracle/gen_golden.py games   --drift --games 48 --seed0 7000
     python3 -B oracle/gen_golden.py mcts    --plies 6
     python3 -B oracle/gen_golden.py net
 
@@ -19,7 +20,8 @@ Fixture families:
                      axial-distance classes, action-slot keys, core_index labels
   games_*.json.gz    random-playout games: per ply the packed position, sorted legal
                      list, next_move_tiles, sparse 56-plane encoding, state_key,
-                     terminal flag/winner and the action taken
+                     terminal flag/winner and the action taken (games_seam: `drift` games, whose hive walks to
+                     the edge of the 12x12 board and over it, where is_straight_line and the torus neighbours disagree)
   mcts.json.gz       HivePlayer (SEARCH_THREADS=1, seeded numpy, stub evaluator)
                      visit counts / chosen action
   mcts_deep.json.gz  the same at 600 simulations without root noise: searches deep enough
@@ -98,12 +100,21 @@ def snapshot(g, with_planes=True):
     return rec
 
 
-def choose(g, rng, policy):
+DRIFT_DIRS = ((1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, -1), (1, -1), (-1, 1))
+
+
+def choose(g, rng, policy, direction=None):
     """Pick the next action.  Policies only bias WHICH legal move is taken so that
-    rarer situations (beetle stacks, surrounded queens, passes) show up."""
+    rarer situations (beetle stacks, surrounded queens, passes, a hive at the board's edge) show up."""
     acts = g.actions()
     if not acts:
         return -1
+    if policy == "drift":    # the destination furthest along this game's direction (index_xy, no wrap): the hive walks to the
+        if rng.random() < 0.30:                                                    # edge of the 12x12 board and over it
+            return int(acts[rng.integers(len(acts))])
+        score = [direction[0] * (a // 11 // 12) + direction[1] * (a // 11 % 12) for a in acts]
+        cand = [a for a, s in zip(acts, score) if s == max(score)]
+        return int(cand[rng.integers(len(cand))])
     if policy == "passy" and g.state.turn > 2 and rng.random() < 0.06:
         return -1            # a voluntary pass: move(-1) is what skip-like callers do (env_hive.py:100-103)
     if policy in ("uniform", "passy") or rng.random() < 0.35:
@@ -134,6 +145,7 @@ def choose(g, rng, policy):
 def play_game(args):
     seed, policy, with_planes = args
     rng = np.random.default_rng(seed)
+    direction = DRIFT_DIRS[rng.integers(len(DRIFT_DIRS))] if policy == "drift" else None   # one per game, from its seed
     g = _new_game()
     plies = []
     while True:
@@ -142,7 +154,7 @@ def play_game(args):
             rec["a"] = None
             plies.append(rec)
             break
-        a = choose(g, rng, policy)
+        a = choose(g, rng, policy, direction)
         rec["a"] = a
         plies.append(rec)
         g.move(a)
@@ -196,7 +208,7 @@ def cmd_tables(_):
 def cmd_games(a):
     import multiprocessing as mp
     jobs = []
-    pols = ["passy"] if a.passy else ["uniform", "beetle", "attack"]
+    pols = ["passy"] if a.passy else ["drift"] if a.drift else ["uniform", "beetle", "attack"]
     for i in range(a.games):
         jobs.append((a.seed0 + i, pols[i % len(pols)], not a.no_planes))
     with mp.Pool(a.procs) as pool:
@@ -206,9 +218,13 @@ def cmd_games(a):
             print(f"[{k + 1}/{len(jobs)}] seed {gm['seed']} {gm['policy']} plies {len(gm['plies'])} "
                   f"over={gm['plies'][-1]['over']} win={gm['plies'][-1]['win']}", flush=True)
     games.sort(key=lambda x: x["seed"])
-    name = a.out or ("games_movegen.json.gz" if a.no_planes else "games_full.json.gz")
-    with gzip.open(os.path.join(GOLD, name), "wt", compresslevel=9) as f:
-        json.dump({"games": games}, f, separators=(",", ":"))
+    name = a.out or ("games_seam.json.gz" if a.drift else "games_movegen.json.gz" if a.no_planes else "games_full.json.gz")
+    if a.drift:      # no time stamp in the gzip header: the same command writes the same bytes
+        with open(os.path.join(GOLD, name), "wb") as raw, gzip.GzipFile("", "wb", 9, raw, mtime=0) as f:
+            f.write(json.dumps({"games": games}, separators=(",", ":")).encode())
+    else:
+        with gzip.open(os.path.join(GOLD, name), "wt", compresslevel=9) as f:
+            json.dump({"games": games}, f, separators=(",", ":"))
     npos = sum(len(g["plies"]) for g in games)
     print(name, "games", len(games), "positions", npos)
 
@@ -583,6 +599,7 @@ if __name__ == "__main__":
     pg.add_argument("--no-planes", action="store_true")
     pg.add_argument("--out", default=None)
     pg.add_argument("--passy", action="store_true", help="games with voluntary passes")
+    pg.add_argument("--drift", action="store_true", help="write games_seam.json.gz: games whose hive walks to the board's edge")
     pm = sub.add_parser("mcts")
     pm.add_argument("--sims", type=int, default=50)
     pd = sub.add_parser("mcts_deep")

@@ -101,10 +101,9 @@ def test_movegen_golden_movegen_set(hv):
     assert bad == 0, f"{bad} of {len(recs)} positions differ"
 
 
-def test_replay_golden_games(hv, golden_games):
-    """step + movegen + encode + terminal + history, ply by ply, against the reference's games."""
+def replay_games(hv, games):
+    """step + movegen + encode + terminal + history, ply by ply, against games of the reference (golden records)."""
     h, batch, packing = hv
-    games = golden_games
     n = len(games)
     B = batch.BoardBatch(n)
     maxlen = max(len(g["plies"]) for g in games)
@@ -146,6 +145,10 @@ def test_replay_golden_games(hv, golden_games):
                 acts[gi] = rec["a"]
         B.step(acts, sync=True)
     B.close()
+
+
+def test_replay_golden_games(hv, golden_games):
+    replay_games(hv, golden_games)
 
 
 def test_encode_variants_agree(hv, golden_games):
@@ -328,13 +331,12 @@ def test_movegen_pair_layout_equals_quad_layout_and_oracle(hv, golden_games):
     assert torch.equal(mq, mp[:16383]) and torch.equal(cq, cp[:16383]) and torch.equal(lq, lp[:16383])
 
 
-def test_random_playout_vs_oracle_lockstep(hv):
-    """256 games stepped on the GPU and in the oracle with the same actions; every ply compared
-    (legal sets, planes, terminal flags), including passes and finished games."""
+def lockstep_vs_oracle(hv, n, rng, pick=None, seen=None):
+    """n games stepped on the GPU and in the oracle with the same actions; every ply compared (legal sets, planes,
+    terminal flags), including passes and finished games.  pick(i, game, legal ids) chooses game i's move (default:
+    uniform over the legal ids, -1 when there is none); seen(game, legal ids, over, winner) is told every position."""
     h, batch, packing = hv
     from oracle import oracle_py as O
-    n = 256 * (8 if os.environ.get("HIVE_TEST_HEAVY") else 1)
-    rng = np.random.default_rng(7)
     B = batch.BoardBatch(n)
     games = [O.OracleGame() for _ in range(n)]
     done = np.zeros(n, dtype=bool)
@@ -353,10 +355,15 @@ def test_random_playout_vs_oracle_lockstep(hv):
             o, w = g.game_is_over()
             assert bool(over[i]) == o and (not o or int(winner[i]) == w), (i, ply)
             assert np.array_equal(planes[i], g.encode_board()), (i, ply)
+            if seen is not None:
+                seen(g, want, o, w)
             if o or g.turn >= 55:
                 done[i] = True
                 continue
-            a = int(want[rng.integers(len(want))]) if want else -1
+            if pick is not None:
+                a = pick(i, g, want)
+            else:
+                a = int(want[rng.integers(len(want))]) if want else -1
             if ply > 2 and rng.random() < 0.04:
                 a = -1          # a forced pass / skip_turn (env_hive.py:100-103,493-496): history must not advance
             acts[i] = a
@@ -366,6 +373,12 @@ def test_random_playout_vs_oracle_lockstep(hv):
         B.step(acts, sync=True)
     assert done.all()
     B.close()
+
+
+def test_random_playout_vs_oracle_lockstep(hv):
+    """256 games under uniform-random moves with 4 % voluntary passes (tests/test_gpu_env_seam.py runs the same body under
+    playouts that reach tall stacks, finished games and the board's seam)."""
+    lockstep_vs_oracle(hv, 256 * (8 if os.environ.get("HIVE_TEST_HEAVY") else 1), np.random.default_rng(7))
 
 
 def test_size_independent_properties_large_batch(hv):
