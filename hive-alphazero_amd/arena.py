@@ -227,6 +227,7 @@ class Arena:
         forced: optional int32[games_in_flight]; entries >= -1 replace the move of that slot (-2 = keep the engine's)."""
         import torch
         from ._lib import check
+        from .mcts import _override
         boards, hist = self.env.export_state()
         nd = self._retire_finished(boards)
         if nd:
@@ -248,9 +249,7 @@ class Arena:
         check(self.L.hive_arena_opening_launch(_p(boards), _p(count), _p(lst), _p(self.pair_id), _p(self.active), self.n,
                                                ctypes.c_uint64(self.seed & (2 ** 64 - 1)), self.opening_turns, _p(action),
                                                stream_ptr(self.device)))
-        if forced is not None:
-            forced = torch.as_tensor(forced, dtype=torch.int32, device=self.device)
-            action = torch.where((forced >= -1) & (action != -2), forced, action)
+        action = _override(action, forced)
         if self.keep_moves:
             col = torch.clamp(turn.long() - 1, 0, MAX_MOVES - 1).view(-1, 1)
             old = self.moves.gather(1, col)

@@ -13,193 +13,7 @@ from . import _lib
 from ._lib import HIVE_MASK_WORDS, HWC, check, dtype_code, load, ptr as _p, stream_ptr
 from .config import MAX_GAME_LENGTH
 from .records import PlyLog, concat_packed, packed_games, rows_from_game, unpack_game
-
-
-PUCT, UCT = 0, 1           # HiveSearchMode (include/hive_search.h)
-LEAF_KINDS = ("unused", "root_evaluated", "expanded_evaluated", "known_finished_game", "collision", "length_cap",
-              "new_finished_or_capped", "already_created_in_flight")
-
-
-BUDGET_STREAM = 0x8CB92BA72F3D8DD7      # stream constant of hive_search_draw_budgets (include/hive_search.h)
-
-
-def full_threshold(p_full):
-    """floor(p_full * 2^32) saturated to 32 bits: what hive_search_draw_budgets compares the draw with (0xFFFFFFFF = always)."""
-    if not 0.0 <= p_full <= 1.0:
-        raise ValueError("p_full must lie in [0, 1]")
-    return min(int(p_full * 4294967296.0), 0xFFFFFFFF)
-
-
-def playout_cap_draw(seed, game_ids, turns, p_full):
-    """bool[n]: is the ply of game game_ids[i] at root turn turns[i] searched in full?  The numpy restatement of
-    hive_search_draw_budgets (no GPU): x = the first output of csrc/hive_rng.hpp's generator keyed by (seed ^ BUDGET_STREAM,
-    game id, turn, 0); full iff (x >> 32) < floor(p_full * 2^32), and always at p_full = 1 (the saturated threshold)."""
-    import numpy as np
-    from .replay import _M64, _splitmix
-    thr = full_threshold(p_full)
-    if thr == 0xFFFFFFFF:
-        return np.ones(len(game_ids), dtype=bool)
-    with np.errstate(over="ignore"):
-        a = np.asarray(game_ids, dtype=np.int64).astype(np.uint64)
-        b = np.asarray(turns, dtype=np.int64).astype(np.uint64)
-        key = np.uint64((int(seed) ^ BUDGET_STREAM) & _M64)
-        s = _splitmix(key ^ _splitmix(a * np.uint64(0x100000001B3) + _splitmix(b * np.uint64(0x9E3779B1))))
-        x = _splitmix(s)
-    return (x >> np.uint64(32)) < np.uint64(thr)
-
-
-def rolling_clock_step(clock, budget, active, slots):
-    """One round of a rolling search in numpy (no GPU): the rule of search_select_kernel's per-game clocks and of
-    hive_search_round_end.  clock / budget int[n], active bool-like[n] -> (takes_part bool[n, slots], clock after the round
-    int64[n], done bool[n]).  An active game at clock c with budget b runs slot sl iff c + sl < b and (c > 0 or sl == 0) -- the
-    root-opening simulation runs alone -- as simulation number c + sl; the round moves its clock by 1 from 0, else by
-    min(slots, b - c); done = active and clock >= budget.  Iterated from 0 this lays a game's simulations out as
-    TreeSearch.run_simulations does for sims = b: 0 alone, then `slots` per round."""
-    import numpy as np
-    c = np.asarray(clock, dtype=np.int64)
-    b = np.asarray(budget, dtype=np.int64)
-    on = np.asarray(active) != 0
-    sl = np.arange(int(slots), dtype=np.int64)[None, :]
-    part = on[:, None] & (c[:, None] + sl < b[:, None]) & ((c[:, None] > 0) | (sl == 0))
-    step = np.where(c == 0, 1, np.minimum(int(slots), b - c))
-    after = np.where(on & (c < b), c + step, c)
-    return part, after, on & (after >= b)
-
-
-def rolling_quantum(sims, slots):
-    """Rounds a rolling search of `sims` simulations takes: the opening one alone, then `slots` per round."""
-    return 1 + -(-(int(sims) - 1) // int(slots))
-
-
-def rolling_options(rolling, search_options, sims, slots, playout_cap=None):
-    """SelfPlay's `rolling` argument checked and completed (no GPU): None for lock step, else {"quantum": rounds per
-    turn-over}.  rolling = None / False, True, or {"quantum": q}; the default quantum is the rounds of the shorter search,
-    rolling_quantum(min(full, fast) with a cap else sims, slots).  search_options with keep_tree are refused with rolling:
-    hive_search_advance_roots moves every tree at once."""
-    if not rolling:
-        return None
-    opt = {} if rolling is True else dict(rolling)
-    if set(opt) - {"quantum"}:
-        raise ValueError("rolling takes True or {'quantum': rounds per turn-over}")
-    if (search_options or {}).get("keep_tree"):
-        raise ValueError("SelfPlay: rolling cannot keep trees (hive_search_advance_roots moves every tree at once)")
-    shortest = min(playout_cap["full"], playout_cap["fast"]) if playout_cap else sims
-    q = int(opt.get("quantum") or rolling_quantum(shortest, slots))
-    if q < 1:
-        raise ValueError("rolling: quantum must be at least 1")
-    return {"quantum": q}
-
-
-# ---- Gumbel root with sequential halving (include/hive_search.h, hive_search_set_gumbel): the numpy statements, no GPU
-GUMBEL_STREAM = 0x6A09E667F3BCC909      # stream constant of the per-edge Gumbel draws
-GUMBEL_DEFAULTS = {"m": 16, "c_visit": 50.0, "c_scale": 1.0}      # c_visit / c_scale: the paper's values, not tuned for this game
-
-
-def gumbel_considered_visits(m, n):
-    """int32[n]: the sequential-halving sequence of considered visits for m considered actions and n simulations (Danihelka
-    et al. 2022, as the published mctx code lays it out).  m <= 1: 0 .. n-1.  Else with L = ceil(log2 m) and k = m: emit
-    max(1, n // (L k)) times the visit counts of the first k slots, incrementing them after each emission, then
-    k = max(2, k // 2), until n entries exist.  Simulation s >= 1 of a search goes to an edge that holds entry s - 1 visits."""
-    import numpy as np
-    m, n = int(m), max(int(n), 0)
-    if m <= 1:
-        return np.arange(n, dtype=np.int32)
-    log2m = (m - 1).bit_length()
-    seq, visits, k = [], [0] * m, m
-    while len(seq) < n:
-        for _ in range(max(1, n // (log2m * k))):
-            seq.extend(visits[:k])
-            for i in range(k):
-                visits[i] += 1
-        k = max(2, k // 2)
-    return np.asarray(seq[:n], dtype=np.int32)
-
-
-def gumbel_draw(seed, game_id, turn, ne, quiet=False):
-    """float64[ne]: g_e = -log(-log(u_e)) of the root of game `game_id` at root turn `turn`; u_e (float32, computed exactly as
-    the device does, like playout_cap_draw's word) is the first uniform of csrc/hive_rng.hpp's generator keyed
-    (seed ^ GUMBEL_STREAM, game id, turn << 40, edge e) -- the noise key at simulation 0, slot 0.  quiet: zeros."""
-    import numpy as np
-    from .replay import _M64, _splitmix
-    ne = int(ne)
-    if quiet:
-        return np.zeros(ne, dtype=np.float64)
-    with np.errstate(over="ignore", divide="ignore"):
-        e = np.arange(ne, dtype=np.uint64)
-        key = np.full(1, (int(seed) ^ GUMBEL_STREAM) & _M64, dtype=np.uint64)
-        a = np.full(1, int(game_id) & _M64, dtype=np.uint64)
-        b = np.full(1, (int(turn) << 40) & _M64, dtype=np.uint64)
-        s = _splitmix(key ^ _splitmix(a * np.uint64(0x100000001B3) + _splitmix(b * np.uint64(0x9E3779B1) + e)))
-        s = _splitmix(s)
-        u = ((s >> np.uint64(40)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
-        return -np.log(-np.log(u.astype(np.float64)))
-
-
-def gumbel_improved_policy(p, n, w, v_root, c_visit=GUMBEL_DEFAULTS["c_visit"], c_scale=GUMBEL_DEFAULTS["c_scale"]):
-    """(logit + sigma(completed q), improved policy) float64[ne] of a root with priors p, visits n, value sums w and the
-    network value v_root: the rule of include/hive_search.h in float64.  The score of an edge is its g plus the first array;
-    the improved policy is the softmax of the first array."""
-    import numpy as np
-    p = np.asarray(p, dtype=np.float64)
-    n = np.asarray(n, dtype=np.int64)
-    w = np.asarray(w, dtype=np.float64)
-    logit = np.log(np.maximum(p, 1e-30))
-    seen = n > 0
-    q = np.where(seen, w / np.maximum(n, 1), 0.0)
-    total, prior_seen = int(n.sum()), float(p[seen].sum())
-    v_mix = float(v_root)
-    if total > 0 and prior_seen > 0.0:
-        v_mix = (float(v_root) + total * float((p[seen] * q[seen]).sum()) / prior_seen) / (1.0 + total)
-    qhat = np.where(seen, q, v_mix)
-    lo, hi = float(qhat.min()), float(qhat.max())
-    sigma = (float(c_visit) + int(n.max())) * float(c_scale) * ((qhat - lo) / max(hi - lo, 1e-8))
-    score = logit + sigma
-    z = np.exp(score - score.max())
-    return score, z / z.sum()
-
-
-def gumbel_options(gumbel, slots=1, mode=PUCT, keep_tree=False):
-    """TreeSearch's `gumbel` argument checked and completed (no GPU): None for off, else {"m", "c_visit", "c_scale"}.
-    gumbel = None / False, True, or a dict with any of those keys (GUMBEL_DEFAULTS fill the rest).  Refused, as
-    hive_search_set_gumbel refuses them: slots > 1 (visits in flight would desynchronise the halving schedule), UCT mode,
-    and kept trees (a carried root has no network value of its own and no fresh schedule)."""
-    if not gumbel:
-        return None
-    opt = {} if gumbel is True else dict(gumbel)
-    if set(opt) - set(GUMBEL_DEFAULTS):
-        raise ValueError("gumbel takes True or a dict with m, c_visit, c_scale")
-    opt = {"m": int(opt.get("m", GUMBEL_DEFAULTS["m"])), "c_visit": float(opt.get("c_visit", GUMBEL_DEFAULTS["c_visit"])),
-           "c_scale": float(opt.get("c_scale", GUMBEL_DEFAULTS["c_scale"]))}
-    if opt["m"] < 1 or not opt["c_visit"] >= 0.0 or not opt["c_scale"] > 0.0:
-        raise ValueError("gumbel: m must be at least 1, c_visit >= 0 and c_scale > 0")
-    if int(slots) > 1:
-        raise ValueError("gumbel: one slot only (visits in flight would desynchronise the sequential-halving schedule)")
-    if mode == UCT:
-        raise ValueError("gumbel: the Gumbel root has no UCT form (PUCT mode only)")
-    if keep_tree:
-        raise ValueError("gumbel: not with keep_tree (a carried root has no network value and no fresh schedule)")
-    return opt
-
-
-def gumbel_interior_options(gumbel_interior, gumbel):
-    """TreeSearch's `gumbel_interior` argument checked (no GPU): True iff the Gumbel rule also selects below the root.  It is an
-    option of the Gumbel root, not a search of its own: without `gumbel` it is refused."""
-    if gumbel_interior and not gumbel:
-        raise ValueError("gumbel_interior: needs the Gumbel root (gumbel=True or its option dict)")
-    return bool(gumbel_interior)
-
-
-def gumbel_interior_choice(p, n, w, v_node, c_visit=GUMBEL_DEFAULTS["c_visit"], c_scale=GUMBEL_DEFAULTS["c_scale"]):
-    """(edge, score float64[ne]) of the Gumbel rule below the root at a node with priors p, visits n, value sums w and the value
-    v_node its position was predicted with (include/hive_search.h, hive_search_set_gumbel_interior), in float64:
-    score = improved policy - n / (1 + sum n); the edge is the first maximum.  A single edge is taken as it is."""
-    import numpy as np
-    n = np.asarray(n, dtype=np.int64)
-    if n.size == 1:
-        return 0, np.zeros(1)
-    _, improved = gumbel_improved_policy(p, n, w, v_node, c_visit, c_scale)
-    score = improved - n / (1.0 + float(n.sum()))
-    return int(np.argmax(score)), score
+from .search_rules import *  # noqa: F401,F403  (the rules' numpy statements; every mcts.NAME of them keeps working)
 
 
 class _GumbelParams(ctypes.Structure):
@@ -365,7 +179,9 @@ class TreeSearch:
 
     def _evaluate(self, k, n, s):
         """The network's (p, v) for the n = k * games leaves of this round of simulations (rows the backup never reads,
-        and duplicates of an evaluated row, are switched off for an evaluator that takes the flags)."""
+        and duplicates of an evaluated row, are switched off for an evaluator that takes the flags), as the evaluator returns
+        them: _round makes them the backup's fp32 rows and, with a store, inserts them into it (hive_leaf_store_update;
+        the lookup happens here, before the network runs)."""
         L = self.L
         if self.skip_unread_rows:
             check(L.hive_search_leaf_need(self._h, k, _p(self.leaf_boards), _p(self.leaf_over), _p(self.leaf_need),
@@ -380,17 +196,51 @@ class TreeSearch:
                     check(L.hive_leaf_store_lookup(self._store, _p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.leaf_keys),
                                                    _p(self.leaf_need), _p(self.leaf_hit), _p(self.evals_run), s))
                 p, v = self.evaluator(self.planes[:n], need=self.leaf_need[:n], rep=self.leaf_rep[:n])
-                if self._store is not None:
-                    p = p.float().contiguous()
-                    v = v.float().contiguous().view(-1)
-                    check(L.hive_leaf_store_update(self._store, _p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.leaf_keys),
-                                                   _p(self.leaf_need), _p(self.leaf_rep), _p(self.leaf_hit), _p(p), _p(v), s))
             else:
                 p, v = self.evaluator(self.planes[:n], need=self.leaf_need[:n])
         else:
             p, v = self.evaluator(self.planes[:n])
         self.evals_launched += n
         return p, v
+
+    def _round(self, k, between=None):
+        """One round of simulations, the only place that issues one: select for slots 0 .. k-1, the leaf launch over the
+        n = k * games rows, between() (a caller's read of the leaf buffers before the network runs), the evaluation and the
+        backup of slots 0 .. k-1.  The handle's stream is the caller's (_stream())."""
+        L, G, s = self.L, self.games, stream_ptr(self.device)
+        for sl in range(k):
+            check(L.hive_search_select(self._h, sl, _p(self.leaf_boards[sl * G:]), _p(self.leaf_hist[sl * G:])))
+        n = k * G
+        check(L.hive_leaf_launch(_p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.planes), dtype_code(self.plane_dtype),
+                                 HWC, _p(self.workspace), _p(self.leaf_mask), _p(self.leaf_count),
+                                 _p(self.leaf_over), _p(self.leaf_winner), s))
+        if between is not None:
+            between()
+        p, v = self._evaluate(k, n, s)
+        p = p.float().contiguous()
+        v = v.float().contiguous().view(-1)
+        if self._store is not None:      # the round's answers join the kept evaluations (fp32 rows, like the backup's)
+            check(L.hive_leaf_store_update(self._store, _p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.leaf_keys),
+                                           _p(self.leaf_need), _p(self.leaf_rep), _p(self.leaf_hit), _p(p), _p(v), s))
+        for sl in range(k):
+            o = sl * G
+            check(L.hive_search_backup(self._h, sl, _p(self.leaf_boards[o:]), _p(self.leaf_hist[o:]),
+                                       _p(self.leaf_mask[o:]), _p(self.leaf_over[o:]), _p(self.leaf_winner[o:]),
+                                       _p(p[o:]), _p(v[o:])))
+
+    def _games_mask(self, x, dtype=torch.int8):
+        """x as a contiguous device tensor of `dtype` with one entry per game."""
+        x = torch.as_tensor(x).to(device=self.device, dtype=dtype).contiguous()
+        assert x.numel() == self.games
+        return x
+
+    def _read(self, fn, *tail, count=1, dtype=torch.int32, alloc=torch.zeros):
+        """One of the library's per-game readers: `count` fresh [games, *tail] tensors filled by fn(handle, out, ...) on the
+        current stream -> the tensor, or the list of them."""
+        out = [alloc((self.games,) + tail, dtype=dtype, device=self.device) for _ in range(count)]
+        self._stream()
+        check(fn(self._h, *[_p(t) for t in out]))
+        return out[0] if count == 1 else out
 
     def advance_roots(self, root_boards, root_hist, active=None, played=None):
         """keep_tree only: the roots of the next search, each tree cut down to the subtree under `played`
@@ -418,11 +268,9 @@ class TreeSearch:
                 host = torch.as_tensor(budgets).reshape(-1)
                 if host.numel() and int(host.max()) > self.sims:
                     raise ValueError(f"TreeSearch: a budget of {int(host.max())} simulations exceeds sims={self.sims}")
-            budgets = torch.as_tensor(budgets).to(device=self.device, dtype=torch.int32).contiguous()
-            assert budgets.numel() == self.games
+            budgets = self._games_mask(budgets, torch.int32)
             if quiet is not None:
-                quiet = torch.as_tensor(quiet).to(device=self.device, dtype=torch.int8).contiguous()
-                assert quiet.numel() == self.games
+                quiet = self._games_mask(quiet)
         self._budgets, self._quiet = budgets, quiet
         check(self.L.hive_search_set_budgets(self._h, _p(budgets), _p(quiet)))
 
@@ -435,8 +283,7 @@ class TreeSearch:
             self.gumbel = self._gumbel_where = self._gumbel_sims = None
             return
         if where is not None:
-            where = torch.as_tensor(where).to(device=self.device, dtype=torch.int8).contiguous()
-            assert where.numel() == self.games
+            where = self._games_mask(where)
         prm = _GumbelParams(opt["m"], opt["c_visit"], opt["c_scale"], int(self.sims))
         check(self.L.hive_search_set_gumbel(self._h, ctypes.byref(prm), _p(where)))
         # (the handle keeps the address of `where`: this object keeps the tensor)
@@ -452,11 +299,7 @@ class TreeSearch:
         """The Gumbel rule below the root on or off, for the Gumbel games with where[g] != 0 (int8 / bool [games]; None =
         every Gumbel game): hive_search_set_gumbel_interior.  It acts on Gumbel games only and survives set_gumbel(None) /
         set_gumbel(...): switching the Gumbel root off and on leaves it as it was."""
-        if on and where is not None:
-            where = torch.as_tensor(where).to(device=self.device, dtype=torch.int8).contiguous()
-            assert where.numel() == self.games
-        else:
-            where = None
+        where = self._games_mask(where) if on and where is not None else None
         check(self.L.hive_search_set_gumbel_interior(self._h, 1 if on else 0, _p(where)))
         # (the handle keeps the address of `where`: this object keeps the tensor)
         self.gumbel_interior, self._gumbel_interior_where = bool(on), where
@@ -474,17 +317,11 @@ class TreeSearch:
     def root_gumbel(self):
         """(g, logit, completed q, improved policy) fp32[games,256] of the roots as they stand, in edge order (ascending
         action id; zeros past the last edge): hive_search_root_gumbel."""
-        out = [torch.zeros((self.games, 256), dtype=torch.float32, device=self.device) for _ in range(4)]
-        self._stream()
-        check(self.L.hive_search_root_gumbel(self._h, *[_p(t) for t in out]))
-        return out
+        return self._read(self.L.hive_search_root_gumbel, 256, count=4, dtype=torch.float32)
 
     def gumbel_fallbacks(self):
         """int32[games]: root selections since create that found no edge at the scheduled visit count."""
-        out = torch.zeros((self.games,), dtype=torch.int32, device=self.device)
-        self._stream()
-        check(self.L.hive_search_gumbel_fallbacks(self._h, _p(out)))
-        return out
+        return self._read(self.L.hive_search_gumbel_fallbacks)
 
     def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False, played=None, budgets=None,
                quiet=None):
@@ -518,31 +355,17 @@ class TreeSearch:
     def run_simulations(self, selfplay=False, keep_root_planes=False):
         """`sims` simulations from the roots as they stand, then the policy: the second half of search()."""
         L, G = self.L, self.games
-        s = self._stream()
+        self._stream()
         if self.gumbel is not None and self._gumbel_sims != self.sims:      # the schedule's length follows `sims`
             self.set_gumbel(self.gumbel, self._gumbel_where)
+
+        def keep_roots():      # the opening round's leaves are the roots
+            self.root_planes = self.workspace[:G * 144].clone()
         done = 0
-        first = True
         while done < self.sims:
-            k = 1 if first else min(self.slots, self.sims - done)      # the first simulation only opens the root
-            for sl in range(k):
-                check(L.hive_search_select(self._h, sl, _p(self.leaf_boards[sl * G:]), _p(self.leaf_hist[sl * G:])))
-            n = k * G
-            check(L.hive_leaf_launch(_p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.planes), dtype_code(self.plane_dtype),
-                                     HWC, _p(self.workspace), _p(self.leaf_mask), _p(self.leaf_count),
-                                     _p(self.leaf_over), _p(self.leaf_winner), s))
-            if first and keep_root_planes:
-                self.root_planes = self.workspace[:G * 144].clone()
-            p, v = self._evaluate(k, n, s)
-            p = p.float().contiguous()
-            v = v.float().contiguous().view(-1)
-            for sl in range(k):
-                o = sl * G
-                check(L.hive_search_backup(self._h, sl, _p(self.leaf_boards[o:]), _p(self.leaf_hist[o:]),
-                                           _p(self.leaf_mask[o:]), _p(self.leaf_over[o:]), _p(self.leaf_winner[o:]),
-                                           _p(p[o:]), _p(v[o:])))
+            k = min(self.slots, self.sims - done) if done else 1      # the first simulation only opens the root
+            self._round(k, keep_roots if keep_root_planes and not done else None)
             done += k
-            first = False
         check(L.hive_search_policy(self._h, _p(self.policy), _p(self.action), _p(self.sum_n), 1 if selfplay else 0))
         return self.action, self.policy, self.sum_n
 
@@ -555,8 +378,7 @@ class TreeSearch:
         """The games with which[g] != 0 (int8 / bool [games]) start a new search from root_boards[g] / root_hist[g], clock 0;
         every other game keeps its tree and its clock (hive_search_restart)."""
         self._need_rolling()
-        which = torch.as_tensor(which).to(device=self.device, dtype=torch.int8).contiguous()
-        assert which.numel() == self.games
+        which = self._games_mask(which)
         self._stream()
         check(self.L.hive_search_restart(self._h, _p(which), _p(root_boards), _p(root_hist), _p(active)))
 
@@ -566,36 +388,24 @@ class TreeSearch:
         keep_root_planes: root_feat int64[games,144] takes the packed feature words of the roots opened in these rounds --
         at clock 0 a game's slot-0 leaf is its root.  Restarts happen between calls, so only the first round can open one."""
         self._need_rolling()
-        L, G, k = self.L, self.games, self.slots
-        s = self._stream()
-        n = k * G
+        L, G = self.L, self.games
+        self._stream()
+
+        def keep_roots():
+            torch.where((self._clock == 0).view(G, 1), self.workspace[:G * 144].view(G, 144), self.root_feat,
+                        out=self.root_feat)
         for r in range(rounds):
-            if keep_root_planes and r == 0:
+            opening = keep_root_planes and r == 0
+            if opening:
                 check(L.hive_search_clocks(self._h, _p(self._clock)))
-            for sl in range(k):
-                check(L.hive_search_select(self._h, sl, _p(self.leaf_boards[sl * G:]), _p(self.leaf_hist[sl * G:])))
-            check(L.hive_leaf_launch(_p(self.leaf_boards), _p(self.leaf_hist), n, _p(self.planes), dtype_code(self.plane_dtype),
-                                     HWC, _p(self.workspace), _p(self.leaf_mask), _p(self.leaf_count),
-                                     _p(self.leaf_over), _p(self.leaf_winner), s))
-            if keep_root_planes and r == 0:
-                torch.where((self._clock == 0).view(G, 1), self.workspace[:G * 144].view(G, 144), self.root_feat,
-                            out=self.root_feat)
-            p, v = self._evaluate(k, n, s)
-            p = p.float().contiguous()
-            v = v.float().contiguous().view(-1)
-            for sl in range(k):
-                o = sl * G
-                check(L.hive_search_backup(self._h, sl, _p(self.leaf_boards[o:]), _p(self.leaf_hist[o:]),
-                                           _p(self.leaf_mask[o:]), _p(self.leaf_over[o:]), _p(self.leaf_winner[o:]),
-                                           _p(p[o:]), _p(v[o:])))
-            check(L.hive_search_round_end(self._h, k, _p(self.done)))
+            self._round(self.slots, keep_roots if opening else None)
+            check(L.hive_search_round_end(self._h, self.slots, _p(self.done)))
         return self.done
 
     def policy_where(self, which, selfplay=False):
         """search()'s answer for the games with which[g] != 0; every other game gets a zero row, action -2 and sum 0
         (hive_search_policy_where).  -> (action, policy, sum_n), buffers of this object."""
-        which = torch.as_tensor(which).to(device=self.device, dtype=torch.int8).contiguous()
-        assert which.numel() == self.games
+        which = self._games_mask(which)
         self._stream()
         check(self.L.hive_search_policy_where(self._h, _p(which), _p(self.policy), _p(self.action), _p(self.sum_n),
                                               1 if selfplay else 0))
@@ -604,45 +414,29 @@ class TreeSearch:
     def clocks(self):
         """int32[games]: the simulations every game's current search has run (hive_search_clocks)."""
         self._need_rolling()
-        out = torch.zeros((self.games,), dtype=torch.int32, device=self.device)
-        self._stream()
-        check(self.L.hive_search_clocks(self._h, _p(out)))
-        return out
+        return self._read(self.L.hive_search_clocks)
 
     def set_game_ids(self, ids):
         """Global game index per tree (int64[games]): the only per-game key of the noise streams (hive_search.h)."""
-        ids = torch.as_tensor(ids, dtype=torch.int64, device=self.device).contiguous()
-        assert ids.numel() == self.games
+        ids = self._games_mask(ids, torch.int64)
         self._stream()
         check(self.L.hive_search_set_game_ids(self._h, _p(ids)))
 
     def root_stats(self):
         """(visits, total_value, priors) fp32[games,1584]: the root's UCTNode arrays (MCTS_chess.py:33-35)."""
-        out = [torch.empty((self.games, 1584), dtype=torch.float32, device=self.device) for _ in range(3)]
-        self._stream()
-        check(self.L.hive_search_root_stats(self._h, _p(out[0]), _p(out[1]), _p(out[2])))
-        return out
+        return self._read(self.L.hive_search_root_stats, 1584, count=3, dtype=torch.float32, alloc=torch.empty)
 
     def leaf_histogram(self):
         """int32[games,8] leaves by kind since create (LEAF_KINDS)."""
-        out = torch.zeros((self.games, 8), dtype=torch.int32, device=self.device)
-        self._stream()
-        check(self.L.hive_search_leaf_histogram(self._h, _p(out)))
-        return out
+        return self._read(self.L.hive_search_leaf_histogram, 8)
 
     def node_counts(self):
-        out = torch.zeros((self.games,), dtype=torch.int32, device=self.device)
-        self._stream()
-        check(self.L.hive_search_node_counts(self._h, _p(out)))
-        return out
+        return self._read(self.L.hive_search_node_counts)
 
     def carry_stats(self):
         """(kept_nodes, carried_visits, refused) int32[games]: nodes / root visits the last search started with (0 = fresh
         tree) and the trees dropped for lack of room in the pool since create (hive_search_carry_stats)."""
-        out = [torch.zeros((self.games,), dtype=torch.int32, device=self.device) for _ in range(3)]
-        self._stream()
-        check(self.L.hive_search_carry_stats(self._h, _p(out[0]), _p(out[1]), _p(out[2])))
-        return out
+        return self._read(self.L.hive_search_carry_stats, count=3)
 
     def export_tree(self, g):
         """Game g's tree as numpy arrays (hive_search_export_tree), cut to its n nodes: {"n", "board" uint8[n,64], "hist"
@@ -664,10 +458,7 @@ class TreeSearch:
 
     def transposition_hits(self):
         """int32[games]: descents that continued through a node first reached by another move order."""
-        out = torch.zeros((self.games,), dtype=torch.int32, device=self.device)
-        self._stream()
-        check(self.L.hive_search_transposition_hits(self._h, _p(out)))
-        return out
+        return self._read(self.L.hive_search_transposition_hits)
 
 
 class ArenaSearch(TreeSearch):
@@ -769,6 +560,8 @@ class ArenaSearch(TreeSearch):
             else:
                 p, v = net["evaluator"](self.planes[:n])
                 self.rows[i] += n
+            # (hive_arena_join_launch takes fp32 rows, so both predictions are converted here; _round's conversion of the
+            # joined pair is then a no-op)
             out.append((p.float().contiguous(), v.float().contiguous().view(-1)))
         (p, v), (pb, vb) = out
         if p.data_ptr() == pb.data_ptr():        # (an evaluator that hands out one static buffer, called twice)
@@ -776,6 +569,15 @@ class ArenaSearch(TreeSearch):
         check(L.hive_arena_join_launch(_p(self._roots), _p(self.a_white), self.games, k, _p(p), _p(v), _p(pb), _p(vb), s))
         self.evals_launched += n
         return p, v
+
+
+def _override(action, forced):
+    """play_ply's `forced` (SelfPlay, Arena): entries >= -1 replace the engine's move of a slot that moves; -2, or
+    forced = None, keep it."""
+    if forced is None:
+        return action
+    forced = torch.as_tensor(forced, dtype=torch.int32, device=action.device)
+    return torch.where((forced >= -1) & (action != -2), forced, action)
 
 
 class SelfPlay:
@@ -997,6 +799,54 @@ class SelfPlay:
         """The k-th waiting finished game as the reference's rows."""
         return self.game_rows(self.finished_games[k])
 
+    def _draw_budgets(self, boards, budget, quiet, full):
+        """Every game's ply at `boards` drawn full or fast from (seed, game id, turn) into budget / quiet / full
+        (hive_search_draw_budgets; idle games get zeros)."""
+        cap = self.playout_cap
+        check(self.search.L.hive_search_draw_budgets(ctypes.c_uint64(self.seed & (2 ** 64 - 1)), _p(self.game_id), _p(boards),
+                                                     _p(self.active), self.games, cap["full"], cap["fast"], cap["threshold"],
+                                                     _p(budget), _p(quiet), _p(full), stream_ptr(self.device)))
+
+    def _log_ply(self, feat, policy, boards, hist, action):
+        """The record route, the only place that issues a record copy: the searched positions (packed features, boards,
+        history), the policies and who moved (action != -2) of this ply join the `records` ring and leave for the log."""
+        mover = (1 - (boards[:, 33] & 1)).to(torch.int8)
+        # (the rolling search's root_feat is rewritten in place at the next turn-over; root_planes is a fresh clone per search)
+        self.records.append((feat.clone() if self.rolling else feat, policy.clone(), mover, self.game_id.clone()))
+        if len(self.records) > 8:
+            self.records.pop(0)
+        # host copies of this ply for the per-game records (8 MB per ply at 1024 games; whole arrays, the per-game
+        # rows are cut out only when a game ends: PlyLog).  They leave asynchronously: a side stream copies into pinned
+        # buffers while the main stream goes on with the env step and the next search (self_play.py:159-160 appends a
+        # row per ply in the game loop itself; here that costs the engine nothing but the PCIe transfer)
+        src = {"feat": feat, "policy": policy, "boards": boards, "hist": hist, "moved": action != -2}
+        if self.playout_cap is not None:
+            src["full"] = self.full             # (redrawn by the next ply, which waits for this copy like the policy buffer)
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))
+        prev_copy = self._copy_done
+        # page-locked staging buffers are recycled: a ply's arrays move to pageable memory one ply later (settle), so
+        # two or three sets exist per engine instead of one per ply of the longest running game (8-32 MB each)
+        host = self._pinned_pool.pop() if self._pinned_pool else \
+            {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True) for k, v in src.items()}
+        with torch.cuda.stream(self._copy_stream):
+            self._copy_stream.wait_event(ready)
+            for k, v in src.items():
+                host[k].copy_(v, non_blocking=True)
+                v.record_stream(self._copy_stream)
+            self._copy_done = torch.cuda.Event()
+            self._copy_done.record(self._copy_stream)
+        # (the arrays are views of the pinned tensors: `host` travels along as the entry's keepalive)
+        log = self._plylog
+        log.append(self.plies, keepalive=host, **{k: v.numpy() for k, v in host.items()})
+        if len(log.entries) >= 2 and prev_copy is not None:
+            # the previous ply's copy was issued a whole search ago: its sparse policies are built now, while the GPU
+            # runs this ply's search (the host has nothing else to do), not when a thousand games end at once
+            prev_copy.synchronize()
+            freed = log.settle(log.entries[-2])
+            if freed is not None:
+                self._pinned_pool.append(freed)
+
     def play_ply(self, forced=None):
         """One move for every game.  Returns the number of games that finished before this move.
         forced: optional int32[games]; entries >= -1 replace the searched move of that slot (replaying a recorded game
@@ -1013,54 +863,13 @@ class SelfPlay:
         if self._played is not None:
             extra["played"] = self._played
         if self.playout_cap is not None:
-            cap = self.playout_cap
-            check(self.search.L.hive_search_draw_budgets(ctypes.c_uint64(self.seed & (2 ** 64 - 1)), _p(self.game_id), _p(boards),
-                                                         _p(self.active), self.games, cap["full"], cap["fast"], cap["threshold"],
-                                                         _p(self.budget), _p(self.quiet), _p(self.full), stream_ptr(self.device)))
+            self._draw_budgets(boards, self.budget, self.quiet, self.full)
             extra["budgets"], extra["quiet"] = self.budget, self.quiet
         action, policy, sum_n = self.search.search(boards, hist, active=self.active, selfplay=True,
                                                    keep_root_planes=self.keep_records, **extra)
         if self.keep_records:
-            mover = (1 - (boards[:, 33] & 1)).to(torch.int8)
-            feat = self.search.root_planes.view(self.games, 144)
-            self.records.append((feat, policy.clone(), mover, self.game_id.clone()))
-            if len(self.records) > 8:
-                self.records.pop(0)
-            # host copies of this ply for the per-game records (8 MB per ply at 1024 games; whole arrays, the per-game
-            # rows are cut out only when a game ends).  They leave asynchronously: a side stream copies into pinned
-            # buffers while the main stream goes on with the env step and the next search (self_play.py:159-160 appends a
-            # row per ply in the game loop itself; here that costs the engine nothing but the PCIe transfer)
-            moved = action != -2
-            src = {"feat": feat, "policy": policy, "boards": boards, "hist": hist, "moved": moved}
-            if self.playout_cap is not None:
-                src["full"] = self.full             # (redrawn by the next ply, which waits for this copy like the policy buffer)
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(self.device))
-            prev_copy = self._copy_done
-            # page-locked staging buffers are recycled: a ply's arrays move to pageable memory one ply later (settle), so
-            # two or three sets exist per engine instead of one per ply of the longest running game (8-32 MB each)
-            host = self._pinned_pool.pop() if self._pinned_pool else \
-                {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True) for k, v in src.items()}
-            with torch.cuda.stream(self._copy_stream):
-                self._copy_stream.wait_event(ready)
-                for k, v in src.items():
-                    host[k].copy_(v, non_blocking=True)
-                    v.record_stream(self._copy_stream)
-                self._copy_done = torch.cuda.Event()
-                self._copy_done.record(self._copy_stream)
-            # (the arrays are views of the pinned tensors: `host` travels along as the entry's keepalive)
-            log = self._plylog
-            log.append(self.plies, keepalive=host, **{k: v.numpy() for k, v in host.items()})
-            if len(log.entries) >= 2 and prev_copy is not None:
-                # the previous ply's copy was issued a whole search ago: its sparse policies are built now, while the GPU
-                # runs this ply's search (the host has nothing else to do), not when a thousand games end at once
-                prev_copy.synchronize()
-                freed = log.settle(log.entries[-2])
-                if freed is not None:
-                    self._pinned_pool.append(freed)
-        if forced is not None:
-            forced = torch.as_tensor(forced, dtype=torch.int32, device=self.device)
-            action = torch.where((forced >= -1) & (action != -2), forced, action)
+            self._log_ply(self.search.root_planes.view(self.games, 144), policy, boards, hist, action)
+        action = _override(action, forced)
         # the env re-derives the legal masks and refuses anything not in them: the search's edges come
         # from the same kernels, so illegal_count() must stay 0 (asserted by the tests)
         self.env.step(action, sync=False)
@@ -1071,7 +880,7 @@ class SelfPlay:
 
     def _play_turnover(self, forced=None):
         """play_ply() of the rolling engine."""
-        L, G, search = self.search.L, self.games, self.search
+        G, search = self.games, self.search
         nd = self._retire_finished()
         boards, hist = self.env.export_state()
         if self._copy_done is not None:
@@ -1081,11 +890,8 @@ class SelfPlay:
         # by a move), draw their budgets and start their next search; every other game keeps its own
         w = self._restart
         if self.playout_cap is not None:
-            cap = self.playout_cap
             budget, quiet, full = self._draw
-            check(L.hive_search_draw_budgets(ctypes.c_uint64(self.seed & (2 ** 64 - 1)), _p(self.game_id), _p(boards),
-                                             _p(self.active), G, cap["full"], cap["fast"], cap["threshold"], _p(budget),
-                                             _p(quiet), _p(full), stream_ptr(self.device)))
+            self._draw_budgets(boards, budget, quiet, full)
             torch.where(w, budget, self.budget, out=self.budget)
             torch.where(w, full, self.full, out=self.full)
             if quiet is not None:
@@ -1096,40 +902,9 @@ class SelfPlay:
         done = search.run_rounds(self.rolling["quantum"], keep_root_planes=self.keep_records)
         action, policy, sum_n = search.policy_where(done, selfplay=True)
         if self.keep_records:
-            roots, rhist = self._root_boards, self._root_hist
-            mover = (1 - (roots[:, 33] & 1)).to(torch.int8)
-            feat = search.root_feat
-            self.records.append((feat.clone(), policy.clone(), mover, self.game_id.clone()))
-            if len(self.records) > 8:
-                self.records.pop(0)
-            # the record route of play_ply: whole arrays leave on the side stream, the rows of the games that moved are cut
-            # out when a game ends (PlyLog).  The entry holds the roots the finished searches started from.
-            moved = action != -2
-            src = {"feat": feat, "policy": policy, "boards": roots, "hist": rhist, "moved": moved}
-            if self.playout_cap is not None:
-                src["full"] = self.full
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(self.device))
-            prev_copy = self._copy_done
-            host = self._pinned_pool.pop() if self._pinned_pool else \
-                {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True) for k, v in src.items()}
-            with torch.cuda.stream(self._copy_stream):
-                self._copy_stream.wait_event(ready)
-                for k, v in src.items():
-                    host[k].copy_(v, non_blocking=True)
-                    v.record_stream(self._copy_stream)
-                self._copy_done = torch.cuda.Event()
-                self._copy_done.record(self._copy_stream)
-            log = self._plylog
-            log.append(self.plies, keepalive=host, **{k: v.numpy() for k, v in host.items()})
-            if len(log.entries) >= 2 and prev_copy is not None:
-                prev_copy.synchronize()
-                freed = log.settle(log.entries[-2])
-                if freed is not None:
-                    self._pinned_pool.append(freed)
-        if forced is not None:
-            forced = torch.as_tensor(forced, dtype=torch.int32, device=self.device)
-            action = torch.where((forced >= -1) & (action != -2), forced, action)
+            # the entry holds the roots the finished searches started from
+            self._log_ply(search.root_feat, policy, self._root_boards, self._root_hist, action)
+        action = _override(action, forced)
         self.env.step(action, sync=False)
         self._restart = action != -2
         self.plies += 1

@@ -20,11 +20,11 @@ import numpy as np
 
 from . import _lib, records
 from .config import DISCOUNTED_REWARD
+from .search_rules import _M64, _splitmix, rng_word  # noqa: F401  (replay._splitmix stays a name of this module)
 
 POLICY_CAP = _lib.HIVE_LIST_CAP          # the most edges a position has = the most entries a stored policy row holds
 MAX_BLOCKS = 2048                        # workgroups of one sample launch; more rows than this take the stride loop
 LAYOUTS = ("chw", "hwc", "nchw_channels_last")
-_M64 = (1 << 64) - 1
 
 
 def discount_table():
@@ -69,25 +69,14 @@ class RingModel:
         return (self.oldest + logical) % self.capacity
 
 
-def _splitmix(x):
-    x = x + np.uint64(0x9E3779B97F4A7C15)
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
-
-
 def draw_indices(seed, step, stream_id, n, live):
     """int64[n]: the logical rows hive_replay_sample draws without an index array.  Entry i is a pure function of
     (seed, step, stream_id, i, live): x = the first output of csrc/hive_rng.hpp's generator keyed by (seed, step,
     stream_id, i); the row is the high half of (x >> 32) * live -- uniform over [0, live) up to 2^-32."""
     if live < 1 or live >= 1 << 32:
         raise ValueError("live must be 1 .. 2^32 - 1")
-    u = lambda v: np.uint64(int(v) & _M64)
-    with np.errstate(over="ignore"):
-        i = np.arange(int(n), dtype=np.uint64)
-        s = _splitmix(u(seed) ^ _splitmix(u(step) * np.uint64(0x100000001B3) + _splitmix(u(stream_id) * np.uint64(0x9E3779B1) + i)))
-        x = _splitmix(s)
-        return (((x >> np.uint64(32)) * np.uint64(live)) >> np.uint64(32)).astype(np.int64)
+    x = rng_word(int(seed), int(step), int(stream_id), np.arange(int(n), dtype=np.uint64))
+    return (((x >> np.uint64(32)) * np.uint64(live)) >> np.uint64(32)).astype(np.int64)
 
 
 def check_packed(packed):

@@ -17,6 +17,8 @@ import os
 import queue as queue_mod
 import time
 
+from . import search_rules      # (numpy only: the child's device is pinned before anything imports torch)
+
 
 def child_device_env(gpu, environ=None):
     """Environment changes that pin a child process to logical GPU `gpu` of THIS process: {name: value or None (= unset)}.
@@ -178,11 +180,11 @@ class SelfPlayWorker:
                     "search_options": dict(search_options) if search_options else None}
         if search_options:
             # refused here, before any child starts, as every child's SelfPlay would refuse it
-            from . import mcts
-            mcts.gumbel_interior_options(
+            search_rules.gumbel_interior_options(
                 search_options.get("gumbel_interior"),
-                mcts.gumbel_options(search_options.get("gumbel"), int(slots), keep_tree=bool(search_options.get("keep_tree"))))
-            mcts.rolling_options(self.cfg["rolling"], search_options, int(sims), int(slots), self.cfg["playout_cap"])
+                search_rules.gumbel_options(search_options.get("gumbel"), int(slots),
+                                            keep_tree=bool(search_options.get("keep_tree"))))
+            search_rules.rolling_options(self.cfg["rolling"], search_options, int(sims), int(slots), self.cfg["playout_cap"])
         if gpus is None:
             import torch
             gpus = list(range(torch.cuda.device_count()))      # counting devices does not initialise HIP

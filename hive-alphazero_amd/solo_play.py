@@ -25,6 +25,7 @@ import numpy as np
 
 from . import config
 from .config import ACTION_SPACE, MAX_GAME_LENGTH, PIECE_BLACK, PIECE_WHITE
+from .search_rules import GUMBEL_DEFAULTS, gumbel_considered_visits, gumbel_improved_policy, gumbel_interior_choice
 
 # woker/solo_play.py:23-30 (module-level knobs, same names so callers can override them the same way)
 simulation_num_per_move = 100
@@ -167,7 +168,7 @@ class HivePlayer:
     # None: the reference.  A dict switches the root to the Gumbel root with sequential halving, the sequential statement of
     # hive_search_set_gumbel (the rule: include/hive_search.h): {"m": 16, "c_visit": 50.0, "c_scale": 1.0, "g": ...}.  "g" is
     # the caller's: an array of one Gumbel draw per root edge (ascending action id), a callable (root turn, edges) -> such an
-    # array (e.g. mcts.gumbel_draw with a seed and game id bound), or None / absent for zeros (a quiet game).  Simulation
+    # array (e.g. search_rules.gumbel_draw with a seed and game id bound), or None / absent for zeros (a quiet game).  Simulation
     # s >= 1 takes the best-scoring root edge among those holding the visit count the schedule asks for, action() plays the
     # best-scoring edge among the most visited and calc_policy() returns the improved policy.  Below the root: PUCT, no noise.
     # SEARCH_THREADS = 1 only; not with keep_tree.  After action(): gumbel_fallbacks = selections that found no edge at the
@@ -175,7 +176,7 @@ class HivePlayer:
     # and the final choice (inf if none).
     # "interior": True -- the Gumbel rule below the root as well (hive_search_set_gumbel_interior): at depth >= 1 the edge is
     # the first maximum of improved policy - n / (1 + sum n), the improved policy taken with the value the entry's position
-    # was predicted with (mcts.gumbel_interior_choice); no noise, no c_puct.  gumbel_min_gap then covers those selections
+    # was predicted with (search_rules.gumbel_interior_choice); no noise, no c_puct.  gumbel_min_gap then covers those selections
     # too, and gumbel_interior_min_gap holds theirs alone.
     gumbel = None
 
@@ -303,7 +304,6 @@ class HivePlayer:
     # ------------------------------------------------------------------ Gumbel root (sequential statement)
     def _gumbel_scores(self, entry, env):
         """(g + logit + sigma, improved policy) over the root's edges."""
-        from .mcts import GUMBEL_DEFAULTS, gumbel_improved_policy
         opt = self.gumbel
         if self._root_g is None:
             g = opt.get("g")
@@ -326,7 +326,6 @@ class HivePlayer:
         return edge
 
     def _gumbel_select(self, entry, env):
-        from .mcts import GUMBEL_DEFAULTS, gumbel_considered_visits
         score, _ = self._gumbel_scores(entry, env)
         m_eff = min(int(self.gumbel.get("m", GUMBEL_DEFAULTS["m"])), len(entry.moves))
         t = int(gumbel_considered_visits(m_eff, self.simulation_num_per_move - 1)[self._cur_sim - 1])
@@ -339,7 +338,6 @@ class HivePlayer:
 
     def _gumbel_interior_select(self, entry):
         """The Gumbel rule below the root: the edge whose visit share lags the improved policy most."""
-        from .mcts import GUMBEL_DEFAULTS, gumbel_interior_choice
         opt = self.gumbel
         edge, score = gumbel_interior_choice(entry.p, entry.n, entry.w, entry.v,
                                              opt.get("c_visit", GUMBEL_DEFAULTS["c_visit"]),
