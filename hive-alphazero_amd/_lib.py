@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "hive_search_set_rolling", "hive_search_round_end", "hive_search_restart", "hive_search_policy_where", "hive_search_clocks",
     "hive_search_set_gumbel", "hive_search_gumbel_schedule", "hive_search_root_gumbel", "hive_search_gumbel_fallbacks",
     "hive_search_set_gumbel_interior", "hive_search_node_values",
+    "hive_search_set_solver", "hive_search_node_status", "hive_search_root_status", "hive_search_solver_stats",
     # include/hive_nn.h
     "hive_nn_conv3x3", "hive_nn_resblock", "hive_nn_conv3x3_dt", "hive_nn_resblock_dt", "hive_nn_tower",
     "hive_nn_conv3x3_sel", "hive_nn_resblock_sel", "hive_nn_copy_rows", "hive_nn_tower72", "hive_nn_compact_rows", "hive_nn_tower72_balanced", "hive_nn_tower72_plan_bytes", "hive_nn_conv72", "hive_nn_conv72_add", "hive_nn_conv72_stats",
@@ -161,6 +162,10 @@ def load():
     L.hive_search_gumbel_fallbacks.argtypes = [vp, vp]
     L.hive_search_set_gumbel_interior.argtypes = [vp, i32, vp]
     L.hive_search_node_values.argtypes = [vp, i32, vp]
+    L.hive_search_set_solver.argtypes = [vp, i32, vp]
+    L.hive_search_node_status.argtypes = [vp, i32, vp, vp]
+    L.hive_search_root_status.argtypes = [vp, vp]
+    L.hive_search_solver_stats.argtypes = [vp, vp]
     L.hive_nn_copy_rows.argtypes = [vp, vp, i32, ctypes.c_longlong, vp]
     L.hive_nn_tower72.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.hive_nn_compact_rows.argtypes = [vp, i32, vp, vp, vp]

@@ -144,11 +144,14 @@ class Arena:
     gumbel_a / gumbel_b (None | True | {"m", "c_visit", "c_scale"}): that side searches with the Gumbel root and plays
     argmax(g + logit + sigma(q)) (mcts.ArenaSearch); the other side's searches are untouched.
     gumbel_interior_a / gumbel_interior_b: that side's Gumbel searches also use the Gumbel rule below the root; it needs
-    the side's gumbel_*.  gumbel_a=True, gumbel_b=True, gumbel_interior_a=True: full Gumbel against root-only Gumbel."""
+    the side's gumbel_*.  gumbel_a=True, gumbel_b=True, gumbel_interior_a=True: full Gumbel against root-only Gumbel.
+    solver_a / solver_b: that side searches with proven wins and losses below the root (mcts.ArenaSearch); not in a match
+    where either side has the Gumbel root."""
 
     def __init__(self, evaluator_a, evaluator_b, pairs=512, sims=50, slots=1, games_in_flight=1024, seed=0, opening_turns=4,
                  noise_eps=0.0, pair_ids=None, keep_moves=True, device=None, search_options=None, sims_b=None,
-                 gumbel_a=None, gumbel_b=None, gumbel_interior_a=False, gumbel_interior_b=False):
+                 gumbel_a=None, gumbel_b=None, gumbel_interior_a=False, gumbel_interior_b=False, solver_a=False,
+                 solver_b=False):
         import torch
         from . import mcts
         from .batch import BoardBatch
@@ -171,7 +174,7 @@ class Arena:
         self.search = mcts.ArenaSearch(G, rounds, evaluator_a, evaluator_b, self.a_white, dev.index, slots, seed,
                                        noise_eps=noise_eps, gumbel_a=gumbel_a, gumbel_b=gumbel_b,
                                        gumbel_interior_a=gumbel_interior_a, gumbel_interior_b=gumbel_interior_b,
-                                       **(search_options or {}))
+                                       solver_a=solver_a, solver_b=solver_b, **(search_options or {}))
         self.budget = torch.zeros((G,), dtype=torch.int32, device=dev) if self.sims_b is not None else None
         self._assign()
         self.result_codes = torch.zeros((G,), dtype=torch.int8, device=dev)

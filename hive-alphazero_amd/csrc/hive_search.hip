@@ -16,7 +16,8 @@
 namespace hive {
 
 constexpr int EC = HIVE_EDGE_CAP;
-enum LeafKind : int8_t { LEAF_NONE = 0, LEAF_ROOT = 1, LEAF_EXPAND = 2, LEAF_TERMINAL = 3, LEAF_COLLISION = 4, LEAF_CAPDRAW = 5 };
+enum LeafKind : int8_t { LEAF_NONE = 0, LEAF_ROOT = 1, LEAF_EXPAND = 2, LEAF_TERMINAL = 3, LEAF_COLLISION = 4, LEAF_CAPDRAW = 5,
+                  LEAF_PROVEN = 8 /* descent ended at a proven node (hive_search_set_solver); histogram bucket [3] */ };
 constexpr float kDrawSentinel = 5.0f;      // solo_play.py:180,183
 
 struct SearchDev {
@@ -58,6 +59,10 @@ struct SearchDev {
     int32_t *gum_fallback;                         // [G] root selections that found no edge at the scheduled visit count
     int gum_int_on;                                // hive_search_set_gumbel_interior: Gumbel games descend by the interior rule ...
     const int8_t *gum_int_where;                   // ... where gum_int_where[g] != 0 (nullptr: every Gumbel game)
+    int solver_on;                                 // hive_search_set_solver: proven wins and losses are on ...
+    const int8_t *solver_where;                    // ... for the games with solver_where[g] != 0 (nullptr: for every game)
+    int8_t *node_status, *e_status;                // [G][MN], [G][MN][EC]; nullptr until the option is first switched on
+    int32_t *solver_stats;                         // [G][4] hive_search_solver_stats
 };
 
 // the node arrays of one pool: hive_search_advance_roots moves the kept subtrees from the handle's pool into a second one
@@ -71,6 +76,7 @@ struct NodePool {
     int16_t *e_act;
     float *e_p, *e_w;
     int32_t *e_n, *e_child;
+    int8_t *node_status, *e_status;                // nullptr until hive_search_set_solver allocates them
 };
 
 // ------------------------------------------------------------------ small device helpers
@@ -154,6 +160,48 @@ constexpr unsigned long long kGumbelStream = 0x6A09E667F3BCC909ull;
 __device__ __forceinline__ bool gumbel_game(const SearchDev &S, int g)
 {
     return S.gum_on && S.prm.mode != HIVE_SEARCH_UCT && (S.gum_where == nullptr || S.gum_where[g] != 0);
+}
+
+// ------------------------------------------------------------------ proven wins and losses (include/hive_search.h, hive_search_set_solver)
+__device__ __forceinline__ bool solver_game(const SearchDev &S, int g)
+{
+    return S.solver_on && S.prm.mode != HIVE_SEARCH_UCT && (S.solver_where == nullptr || S.solver_where[g] != 0);
+}
+// a status holds on a path whose current turn is `turn` iff the finished position lies within the length cap
+__device__ __forceinline__ bool solver_holds(int x, int turn, int cap)
+{
+    return x != 0 && turn + (x < 0 ? -x : x) - 1 <= cap;
+}
+// lanes of one wave see each other's LDS / global writes made before this point
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// The statuses of a node's edges, four per lane (edge e = lane + 64 k in es[k], 0 past the last edge), `own` standing in
+// for edge `at` (the one this backup just wrote): the node's status -- the fastest win if any edge wins, the longest
+// resistance if every edge loses, else unknown.
+__device__ __forceinline__ int wave_solver_node_status(const int8_t *es_row, int ne, int at, int own, int lane)
+{
+    int minpos = 128, maxabs = 0;
+    bool open = false;                                       // an edge of mine that is not a proven loss
+    for (int k = 0; k < 4; ++k) {
+        const int e = lane + 64 * k;
+        if (e < ne) {
+            const int x = e == at ? own : (int)es_row[e];
+            if (x > 0 && x < minpos) minpos = x;
+            if (x >= 0) open = true;
+            if (-x > maxabs) maxabs = -x;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const int a = __shfl_xor(minpos, o), b = __shfl_xor(maxabs, o);
+        minpos = a < minpos ? a : minpos;
+        maxabs = b > maxabs ? b : maxabs;
+    }
+    if (minpos < 128) return minpos;
+    return __ballot(open) == 0ull ? -maxabs : 0;
 }
 
 // entry i of the sequential-halving sequence of considered visits for m >= 1 considered actions and n simulations: the
@@ -378,9 +426,29 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
     const bool quiet = S.quiet != nullptr && S.quiet[g] != 0;
     const bool gumbel = gumbel_game(S, g);
     const bool interior = gumbel && S.gum_int_on && (S.gum_int_where == nullptr || S.gum_int_where[g] != 0);
+    const bool solver = solver_game(S, g);
     while (true) {
         if (S.node_term[nbase + node]) { kind = LEAF_TERMINAL; leafnode = node; break; }          // game over (solo_play.py:169-180)
         if ((int)reinterpret_cast<const uint8_t *>(st)[33] >= S.prm.max_game_length) { kind = LEAF_CAPDRAW; break; }   // :181-183
+        unsigned banned = 0u;                                // bit k: edge lane + 64 k is a proven loss that holds here
+        if (solver) {
+            // a proven node ends the descent like a finished game; at a node passed through, the moves proven to lose are
+            // left out unless every move is one
+            const int turn = (int)reinterpret_cast<const uint8_t *>(st)[33];
+            if (solver_holds(S.node_status[nbase + node], turn, S.prm.max_game_length)) { kind = LEAF_PROVEN; leafnode = node; break; }
+            const int ne_s = S.node_nedge[nbase + node];
+            const int8_t *es = S.e_status + (nbase + node) * EC;
+            bool open = false;
+            for (int k = 0; k < 4; ++k) {
+                const int e = lane + 64 * k;
+                if (e < ne_s) {
+                    const int x = es[e];
+                    if (x < 0 && solver_holds(x, turn, S.prm.max_game_length)) banned |= 1u << k;
+                    else open = true;
+                }
+            }
+            if (__ballot(open) == 0ull) banned = 0u;
+        }
         const int ne = S.node_nedge[nbase + node];
         const long long eb = (nbase + node) * EC;
         const bool uct = S.prm.mode == HIVE_SEARCH_UCT;
@@ -441,7 +509,7 @@ search_select_kernel(SearchDev S, int slot, unsigned long long sim, HiveBoard *_
         } else {
             for (int k = 0; k < 4; ++k) {
                 int e = lane + 64 * k;
-                if (e < ne) {
+                if (e < ne && !((banned >> k) & 1u)) {
                     float p = S.e_p[eb + e], w = S.e_w[eb + e];
                     int n = S.e_n[eb + e];
                     float b;
@@ -538,8 +606,17 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
     int stat = kind;                                        // hive_search_leaf_histogram bucket
     if (kind == LEAF_EXPAND && !capped && S.merge)          // another in-flight slot may have created this position meanwhile
         known = tt_find(S, g, reinterpret_cast<const uint32_t *>(&leaf_boards[g]), lane);
+    const bool solver = solver_game(S, g);
+    int proven = 0;                                         // status of the node where the path ended (wave-uniform)
     if (kind == LEAF_TERMINAL) {
         ret = S.node_tv[nbase + S.leaf_node[sg]];
+        if (solver) proven = S.node_status[nbase + S.leaf_node[sg]];
+    } else if (kind == LEAF_PROVEN) {
+        // the descent stopped at a proven node: a known finished game, |status| - 1 plies early
+        proven = S.node_status[nbase + S.leaf_node[sg]];
+        ret = proven > 0 ? 1.0f : -1.0f;
+        stat = LEAF_TERMINAL;
+        if (lane == 0) S.solver_stats[g * 4 + 0] += 1;
     } else if (capped) {
         // length cap (solo_play.py:181-183): a property of this path's turn count, not of the position -- no node
         if (kind == LEAF_EXPAND && lane == 0) S.e_child[(nbase + S.leaf_node[sg]) * EC + S.leaf_edge[sg]] = -1;
@@ -548,6 +625,7 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
     } else if (known >= 0) {
         if (lane == 0) S.e_child[(nbase + S.leaf_node[sg]) * EC + S.leaf_edge[sg]] = known;
         ret = S.node_term[nbase + known] ? S.node_tv[nbase + known] : v[g];
+        if (solver) proven = S.node_status[nbase + known];
         stat = 7;
     } else {
         const int id = (kind == LEAF_ROOT) ? 0 : S.n_nodes[g];
@@ -558,6 +636,7 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
         const int stm = (turn & 1u) ? 0 : 1;
         bool term = false;
         float tv = 0.f;
+        int fresh = 0;                                      // the new node's status
         if (over[g] && uct) {
             // MCTS_chess.py:144-146: a finished game is never expanded; every visit backs up the network's value of
             // that same position -- the evaluator is a pure function of the planes, so the value is kept with the node
@@ -567,6 +646,7 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
             term = true;
             int w = winner[g];
             tv = (w == 0) ? kDrawSentinel : ((w - 1) == stm ? 1.0f : -1.0f);
+            fresh = (w == 0) ? 0 : ((w - 1) == stm ? 1 : -1);   // only a finished game with a winner proves anything
             stat = 6;
         } else if ((int)turn >= S.prm.max_game_length) {    // solo_play.py:181-183
             term = true;
@@ -600,6 +680,7 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
                         S.e_n[eb + pos] = 0;
                         S.e_w[eb + pos] = 0.f;
                         S.e_child[eb + pos] = -1;
+                        if (S.e_status != nullptr) S.e_status[eb + pos] = 0;
                     }
                 }
                 total += __popcll(w);
@@ -610,7 +691,10 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
                 term = true;
                 tv = v[g];
             } else if (ne == 0) {                           // no legal move: the pass edge (solo_play.py:299-300)
-                if (lane == 0) { S.e_act[eb] = -1; S.e_p[eb] = 0.f; S.e_n[eb] = 0; S.e_w[eb] = 0.f; S.e_child[eb] = -1; }
+                if (lane == 0) {
+                    S.e_act[eb] = -1; S.e_p[eb] = 0.f; S.e_n[eb] = 0; S.e_w[eb] = 0.f; S.e_child[eb] = -1;
+                    if (S.e_status != nullptr) S.e_status[eb] = 0;
+                }
                 ne = 1;
             }
         }
@@ -621,10 +705,12 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
             S.node_term[nbase + id] = term ? 1 : 0;
             S.node_tv[nbase + id] = tv;
             S.node_v[nbase + id] = term ? tv : v[g];            // the interior Gumbel rule completes unvisited edges with it
+            if (S.node_status != nullptr) S.node_status[nbase + id] = (int8_t)fresh;
             S.n_nodes[g] = id + 1;
             if (kind == LEAF_EXPAND) S.e_child[(nbase + S.leaf_node[sg]) * EC + S.leaf_edge[sg]] = id;
         }
         ret = term ? tv : v[g];
+        if (solver) proven = fresh;
     }
     if (lane == 0) {
         S.kind_hist[g * 8 + stat] += 1;
@@ -648,6 +734,24 @@ search_backup_kernel(SearchDev S, int slot, const HiveBoard *__restrict__ leaf_b
                 val = reach_max ? kDrawSentinel : leaf_v;   // solo_play.py:244-247
             }
         }
+    }
+    // proven results travel up this path (include/hive_search.h): the whole wave walks it, four edges per lane and a ballot
+    // decide a node.  Backups run slot after slot, so no other wave writes this game's statuses meanwhile.
+    int c = proven;
+    for (int d = plen - 1; d >= 0 && c != 0 && c > -127 && c < 127; --d) {
+        const int P = pnode[d], k = pedge[d];
+        const long long eb = (nbase + P) * EC;
+        const int own = c > 0 ? -(c + 1) : 1 - c;           // -sign(c) (|c| + 1)
+        const int s = wave_solver_node_status(S.e_status + eb, S.node_nedge[nbase + P], k, own, lane);
+        if (lane == 0) {
+            const int old = S.node_status[nbase + P];
+            S.e_status[eb + k] = (int8_t)own;
+            S.node_status[nbase + P] = (int8_t)s;
+            if (old == 0 && s > 0) S.solver_stats[g * 4 + 1] += 1;
+            if (old == 0 && s < 0) S.solver_stats[g * 4 + 2] += 1;
+        }
+        wave_sync();                                         // a path may pass through P again further up
+        c = s;
     }
 }
 
@@ -706,6 +810,35 @@ search_policy_kernel(SearchDev S, const int8_t *__restrict__ which, float *__res
     // (get_policy) has no such rule -- before the first backed-up visit its policy is all zero
     const bool uct = S.prm.mode == HIVE_SEARCH_UCT;
     const bool use_prior = uct ? false : ((wmax < 0.f) || nsum == 0);
+    const unsigned turn = S.node_board[nbase].turn;
+    // proven wins and losses (include/hive_search.h): a root whose status holds answers from the proof; otherwise the
+    // moves proven to lose leave the choice below -- never the policy row -- unless every move is one
+    unsigned banned = 0u;                                   // bit k: edge lane + 64 k is a proven loss that holds
+    int from_proof = -1;
+    if (solver_game(S, g)) {
+        const int cap = S.prm.max_game_length, s0 = S.node_status[nbase];
+        const bool root_holds = solver_holds(s0, (int)turn, cap);
+        const int8_t *es = S.e_status + eb;
+        long long key = -1;                                 // (speed of the proof, visits, lower edge first), larger is better
+        bool open = false;
+        for (int k = 0; k < 4; ++k) {
+            const int e = lane + 64 * k;
+            if (e < ne) {
+                const int x = es[e];
+                const bool holds = solver_holds(x, (int)turn, cap);
+                if (x < 0 && holds) banned |= 1u << k;
+                else open = true;
+                if (root_holds && holds && (s0 > 0) == (x > 0)) {
+                    const long long speed = s0 > 0 ? 128 - x : -x;
+                    const long long kk = (speed << 40) | ((long long)S.e_n[eb + e] << 8) | (long long)(255 - e);
+                    key = kk > key ? kk : key;
+                }
+            }
+        }
+        if (__ballot(open) == 0ull) banned = 0u;
+        for (int o = 32; o > 0; o >>= 1) { const long long x = __shfl_xor(key, o); key = x > key ? x : key; }
+        if (root_holds && key >= 0) from_proof = 255 - (int)(key & 255);
+    }
     float pi[4];
     float best = -1.f;
     int bidx = 0x7FFFFFFF;
@@ -716,12 +849,19 @@ search_policy_kernel(SearchDev S, const int8_t *__restrict__ which, float *__res
             pi[k] = use_prior ? S.e_p[eb + e] : (nsum > 0 ? (float)S.e_n[eb + e] / (float)nsum : 0.f);
             int a = S.e_act[eb + e];
             if (pol && a >= 0) pol[a] = pi[k];
-            if (pi[k] > best) { best = pi[k]; bidx = e; }
+            if (((banned >> k) & 1u) == 0u && pi[k] > best) { best = pi[k]; bidx = e; }
         }
     }
     wave_argmax(best, bidx);                                // tau < 0.1 always => argmax (solo_play.py:338-345)
     int chosen = bidx;
-    const unsigned turn = S.node_board[nbase].turn;
+    if (from_proof >= 0) {
+        if (lane == 0) {
+            action[g] = S.e_act[eb + from_proof];
+            if (sum_n_out) sum_n_out[g] = nsum;
+            S.solver_stats[g * 4 + 3] += 1;
+        }
+        return;
+    }
     if (selfplay && S.e_act[eb] >= 0) {
         // self_play.py:143-157: e = 0.7 - int(turn+1)/2 * 0.15; resample while e >= 0.1 (turns 1..6)
         float err = 0.7f - 0.5f * (float)(turn + 1u) * 0.15f;
@@ -738,7 +878,11 @@ search_policy_kernel(SearchDev S, const int8_t *__restrict__ which, float *__res
             }
             tot = wave_sum(tot);
             float inv = tot > 0.f ? 1.0f / tot : 0.f, psum = 0.f;
-            for (int k = 0; k < 4; ++k) { nz[k] = (1.0f - err) * pi[k] + err * nz[k] * inv; psum += nz[k]; }
+            for (int k = 0; k < 4; ++k) {
+                nz[k] = (1.0f - err) * pi[k] + err * nz[k] * inv;
+                if ((banned >> k) & 1u) nz[k] = 0.f;        // a move proven to lose is not drawn
+                psum += nz[k];
+            }
             psum = wave_sum(psum);
             Rng r = noise_rng(S.seed ^ 0xA24BAED4963EE407ull, S.game_id[g], turn, 0ull, 0, 7777);
             float target = r.uniform() * psum;
@@ -815,6 +959,16 @@ search_root_stats_kernel(SearchDev S, float *__restrict__ visits, float *__restr
         if (total_value) total_value[row + a] = S.e_w[eb + e];
         if (priors) priors[row + a] = S.e_p[eb + e];
     }
+}
+
+// hive_search_root_status: one thread per game
+__global__ void __launch_bounds__(256)
+search_root_status_kernel(SearchDev S, int8_t *__restrict__ status)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= S.G) return;
+    const bool tree = S.node_status != nullptr && S.active[g] && S.n_nodes[g] > 0;
+    status[g] = tree ? S.node_status[(long long)g * S.MN] : (int8_t)0;
 }
 
 // hive_search_sample_noise: one wave per draw, the same wave_dirichlet / mixing arithmetic as search_select_kernel
@@ -906,14 +1060,6 @@ search_round_end_kernel(SearchDev S, int slots_run, int8_t *__restrict__ done)
         S.clock[g] = c;
     }
     done[g] = (on && c >= b) ? 1 : 0;
-}
-
-// lanes of one wave see each other's LDS / global writes made before this point
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // hive_search_advance_roots: the subtree under the played root edge becomes the tree of the next search.  One wave per
@@ -1017,8 +1163,10 @@ search_advance_kernel(SearchDev S, NodePool D, const int32_t *__restrict__ playe
             D.node_term[dn] = S.node_term[so];
             D.node_tv[dn] = S.node_tv[so];
             D.node_v[dn] = S.node_v[so];
+            if (S.node_status != nullptr) D.node_status[dn] = S.node_status[so];
         }
         for (int e = lane; e < ne; e += 64) {
+            if (S.e_status != nullptr) D.e_status[dn * EC + e] = S.e_status[so * EC + e];
             D.e_act[dn * EC + e] = S.e_act[so * EC + e];
             D.e_p[dn * EC + e] = S.e_p[so * EC + e];
             D.e_n[dn * EC + e] = S.e_n[so * EC + e];
@@ -1066,7 +1214,7 @@ struct HiveSearch {
     int device = 0;
     hipStream_t stream = nullptr;
     unsigned long long sim = 0;
-    void *pool[64];
+    void *pool[72];
     int npool = 0;
     NodePool alt{};             // second node pool of hive_search_advance_roots, allocated on first use
     bool have_alt = false;
@@ -1128,6 +1276,8 @@ static int search_alloc(HiveSearch *s, int games, int max_nodes, int slots)
     S_TRY(alloc(s, &d.gum_fallback, (size_t)games));
     S_TRY(hipMemset(d.root_v, 0, sizeof(float) * (size_t)games));
     S_TRY(hipMemset(d.gum_fallback, 0, sizeof(int32_t) * (size_t)games));
+    S_TRY(alloc(s, &d.solver_stats, (size_t)games * 4));
+    S_TRY(hipMemset(d.solver_stats, 0, sizeof(int32_t) * (size_t)games * 4));
     {
         long long *ids = new (std::nothrow) long long[games];
         if (ids == nullptr) return hive::set_error(HIVE_E_DEVICE, "hive_search_create: out of host memory");
@@ -1199,6 +1349,8 @@ int hive_search_set_params(HiveSearch *s, const HiveSearchParams *p)
         return hive::set_error(HIVE_E_ARG, "hive_search_set_params: unknown mode, negative virtual loss or length cap outside 1..250");
     if (s->d.gum_on && p->mode == HIVE_SEARCH_UCT)
         return hive::set_error(HIVE_E_ARG, "hive_search_set_params: the Gumbel root is on and has no UCT form (hive_search_set_gumbel)");
+    if (s->d.solver_on && p->mode == HIVE_SEARCH_UCT)
+        return hive::set_error(HIVE_E_ARG, "hive_search_set_params: proven results are on and have no UCT form (hive_search_set_solver)");
     s->d.prm = *p;
     return HIVE_OK;
 }
@@ -1281,6 +1433,9 @@ int hive_search_set_gumbel(HiveSearch *s, const HiveGumbelParams *prm, const int
     }
     if (s->d.prm.mode == HIVE_SEARCH_UCT)
         return hive::set_error(HIVE_E_ARG, "hive_search_set_gumbel: the Gumbel root has no UCT form (PUCT mode only)");
+    if (s->d.solver_on)
+        return hive::set_error(HIVE_E_ARG, "hive_search_set_gumbel: not with proven results (hive_search_set_solver): a proven root "
+                                           "ends descents at depth 0 and the halving schedule counts root visits");
     if (s->d.L > 1)
         return hive::set_error(HIVE_E_ARG, "hive_search_set_gumbel: one slot only -- visits in flight would desynchronise the "
                                            "sequential-halving schedule");
@@ -1299,6 +1454,72 @@ int hive_search_set_gumbel_interior(HiveSearch *s, int on, const int8_t *where)
     // read by Gumbel games alone (gumbel_game): accepted before or after hive_search_set_gumbel, in any mode
     s->d.gum_int_on = on ? 1 : 0;
     s->d.gum_int_where = on ? where : nullptr;
+    return HIVE_OK;
+}
+
+int hive_search_set_solver(HiveSearch *s, int on, const int8_t *where)
+{
+    if (!s) return hive::set_error(HIVE_E_ARG, "null handle");
+    if (!on) {
+        s->d.solver_on = 0;
+        s->d.solver_where = nullptr;
+        return HIVE_OK;
+    }
+    if (s->d.prm.mode == HIVE_SEARCH_UCT)
+        return hive::set_error(HIVE_E_ARG, "hive_search_set_solver: proven results have no UCT form (PUCT mode only)");
+    if (s->d.gum_on)
+        return hive::set_error(HIVE_E_ARG, "hive_search_set_solver: not with the Gumbel root (hive_search_set_gumbel): its halving "
+                                           "schedule counts root visits and a proven root ends descents at depth 0");
+    S_TRY(hipSetDevice(s->device));
+    if (s->d.node_status == nullptr) {
+        // both pools at once: hive_search_advance_roots moves the statuses with the nodes, whichever call came first
+        const size_t GN = (size_t)s->d.G * s->d.MN, GE = GN * EC;
+        int8_t *ns[2] = {nullptr, nullptr}, *es[2] = {nullptr, nullptr};
+        for (int i = 0; i < 2; ++i) {
+            S_TRY(alloc(s, &ns[i], GN));
+            S_TRY(alloc(s, &es[i], GE));
+            S_TRY(hipMemsetAsync(ns[i], 0, GN, s->stream));
+            S_TRY(hipMemsetAsync(es[i], 0, GE, s->stream));
+        }
+        s->d.e_status = es[0];
+        s->alt.e_status = es[1];
+        s->alt.node_status = ns[1];
+        s->d.node_status = ns[0];
+    }
+    s->d.solver_where = where;
+    s->d.solver_on = 1;
+    return HIVE_OK;
+}
+
+int hive_search_node_status(HiveSearch *s, int game, int8_t *node, int8_t *edge)
+{
+    if (!s || game < 0 || game >= s->d.G) return hive::set_error(HIVE_E_ARG, "hive_search_node_status: bad argument");
+    S_TRY(hipSetDevice(s->device));
+    const size_t N = (size_t)s->d.MN, o = (size_t)game * N;
+    if (s->d.node_status == nullptr) {
+        if (node) S_TRY(hipMemsetAsync(node, 0, N, s->stream));
+        if (edge) S_TRY(hipMemsetAsync(edge, 0, N * EC, s->stream));
+        return HIVE_OK;
+    }
+    if (node) S_TRY(hipMemcpyAsync(node, s->d.node_status + o, N, hipMemcpyDeviceToDevice, s->stream));
+    if (edge) S_TRY(hipMemcpyAsync(edge, s->d.e_status + o * EC, N * EC, hipMemcpyDeviceToDevice, s->stream));
+    return HIVE_OK;
+}
+
+int hive_search_root_status(HiveSearch *s, int8_t *status)
+{
+    if (!s || !status) return hive::set_error(HIVE_E_ARG, "null argument");
+    S_TRY(hipSetDevice(s->device));
+    hipLaunchKernelGGL(search_root_status_kernel, dim3((unsigned)((s->d.G + 255) / 256)), dim3(256), 0, s->stream, s->d, status);
+    S_TRY(hipGetLastError());
+    return HIVE_OK;
+}
+
+int hive_search_solver_stats(HiveSearch *s, int32_t *out)
+{
+    if (!s || !out) return hive::set_error(HIVE_E_ARG, "null argument");
+    S_TRY(hipSetDevice(s->device));
+    S_TRY(hipMemcpyAsync(out, s->d.solver_stats, sizeof(int32_t) * (size_t)s->d.G * 4, hipMemcpyDeviceToDevice, s->stream));
     return HIVE_OK;
 }
 
@@ -1398,11 +1619,11 @@ int hive_search_advance_roots(HiveSearch *s, const int32_t *played, const HiveBo
     S_TRY(hipGetLastError());
     // every later launch (stream order) works on the pool the kernel wrote
     const NodePool old{d.node_board, d.node_hist, d.node_nedge, d.node_sum_n, d.node_term, d.node_tv, d.node_v,
-                       d.e_act, d.e_p, d.e_w, d.e_n, d.e_child};
+                       d.e_act, d.e_p, d.e_w, d.e_n, d.e_child, d.node_status, d.e_status};
     const NodePool &a = s->alt;
     d.node_board = a.node_board; d.node_hist = a.node_hist; d.node_nedge = a.node_nedge; d.node_sum_n = a.node_sum_n;
     d.node_term = a.node_term; d.node_tv = a.node_tv; d.node_v = a.node_v; d.e_act = a.e_act; d.e_p = a.e_p; d.e_w = a.e_w;
-    d.e_n = a.e_n; d.e_child = a.e_child;
+    d.e_n = a.e_n; d.e_child = a.e_child; d.node_status = a.node_status; d.e_status = a.e_status;
     s->alt = old;
     s->sim = 0;
     return HIVE_OK;

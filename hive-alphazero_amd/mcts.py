@@ -14,6 +14,7 @@ from ._lib import HIVE_MASK_WORDS, HWC, check, dtype_code, load, ptr as _p, stre
 from .config import MAX_GAME_LENGTH
 from .records import PlyLog, concat_packed, packed_games, rows_from_game, unpack_game
 from .search_rules import *  # noqa: F401,F403  (the rules' numpy statements; every mcts.NAME of them keeps working)
+from .search_rules import solver_answer, solver_edge_status, solver_holds, solver_node_status, solver_options  # noqa: F401
 
 
 class _GumbelParams(ctypes.Structure):
@@ -34,7 +35,7 @@ class TreeSearch:
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  c_puct=0.7, noise_eps=0.25, dirichlet_alpha=0.3, max_nodes=None, transpositions=True, mode=PUCT,
                  virtual_loss=None, max_game_length=None, skip_unread_rows=True, share_equal_leaves=True, reuse_store=0,
-                 keep_tree=False, rolling=False, gumbel=None, gumbel_interior=False):
+                 keep_tree=False, rolling=False, gumbel=None, gumbel_interior=False, solver=False):
         """mode = PUCT: woker/solo_play.py::HivePlayer; mode = UCT: alpha_zero/MCTS_chess.py::UCT_search (plain tree, no
         noise, no length cap; with one slot the virtual loss is 0 so that W sums exactly like the sequential reference).
 
@@ -61,8 +62,17 @@ class TreeSearch:
         (hive_search_set_gumbel_interior): at every deeper node the descent takes the edge whose visit share lags
         softmax(logit + sigma(completed q)) most, unvisited children completed by the node's mixed value, in place of PUCT.
         Deterministic, no c_puct; the root's schedule and answer are unchanged.  set_gumbel_interior(on, where) switches it
-        and restricts it to some of the Gumbel games."""
+        and restricts it to some of the Gumbel games.
+
+        solver = True: proven wins and losses below the root (hive_search_set_solver; the rule is stated in
+        include/hive_search.h).  A finished game with a winner proves its node, the proof travels up the path of the
+        simulation that found it, a proven node ends later descents without a network row, moves proven to lose are left out
+        of PUCT and of the answer, and a proven root answers with the fastest win or the longest resistance.  The policy row
+        and sum_n stay the visit distribution.  Draws and the length cap prove nothing.  Works with slots > 1, budgets,
+        rolling and keep_tree; refused in UCT mode and together with gumbel (solver_options).  set_solver(on, where)
+        switches it and restricts it to some games; the others are searched as without it, bit for bit."""
         gumbel = gumbel_options(gumbel, slots, mode, keep_tree)
+        solver = solver_options(solver, mode, gumbel)
         gumbel_interior = gumbel_interior_options(gumbel_interior, gumbel)
         if rolling and keep_tree:
             raise ValueError("TreeSearch: rolling cannot keep trees (hive_search_advance_roots moves every tree at once)")
@@ -107,6 +117,9 @@ class TreeSearch:
         self.gumbel_interior, self._gumbel_interior_where = False, None
         if gumbel_interior:
             self.set_gumbel_interior(True)
+        self.solver, self._solver_where = False, None
+        if solver:
+            self.set_solver(True)
         n = games * slots
         dev = self.device
         self.plane_dtype = plane_dtype
@@ -278,6 +291,8 @@ class TreeSearch:
         """Switch the Gumbel root on (True or the option dict of __init__), for the games with where[g] != 0 (int8 / bool
         [games]; None = every game), or off (None / False): hive_search_set_gumbel."""
         opt = gumbel_options(gumbel, self.slots, self.mode, self.keep_tree)
+        if opt is not None:
+            solver_options(getattr(self, "solver", False), self.mode, opt)
         if opt is None:
             check(self.L.hive_search_set_gumbel(self._h, None, None))
             self.gumbel = self._gumbel_where = self._gumbel_sims = None
@@ -303,6 +318,37 @@ class TreeSearch:
         check(self.L.hive_search_set_gumbel_interior(self._h, 1 if on else 0, _p(where)))
         # (the handle keeps the address of `where`: this object keeps the tensor)
         self.gumbel_interior, self._gumbel_interior_where = bool(on), where
+
+    def set_solver(self, on=True, where=None):
+        """Proven wins and losses on or off, for the games with where[g] != 0 (int8 / bool [games]; None = every game):
+        hive_search_set_solver."""
+        on = solver_options(bool(on), self.mode, self.gumbel)
+        where = self._games_mask(where) if on and where is not None else None
+        self._stream()
+        check(self.L.hive_search_set_solver(self._h, 1 if on else 0, _p(where)))
+        # (the handle keeps the address of `where`: this object keeps the tensor)
+        self.solver, self._solver_where = on, where
+
+    def node_status(self, game):
+        """(node int8[n], edge int8[n,256]): the statuses of game `game`'s tree in export_tree's node and edge order
+        (hive_search_node_status); of a node's edge row only the first nedge entries are meaningful."""
+        node = torch.zeros((self.max_nodes,), dtype=torch.int8, device=self.device)
+        edge = torch.zeros((self.max_nodes, 256), dtype=torch.int8, device=self.device)
+        count = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._stream()
+        check(self.L.hive_search_node_status(self._h, int(game), _p(node), _p(edge)))
+        check(self.L.hive_search_export_tree(self._h, int(game), _p(count), *([None] * 11)))
+        n = int(count.item())
+        return node[:n].cpu().numpy(), edge[:n].cpu().numpy()
+
+    def root_status(self):
+        """int8[games]: the stored status of every root (hive_search_root_status)."""
+        return self._read(self.L.hive_search_root_status, dtype=torch.int8)
+
+    def solver_stats(self):
+        """int32[games,4] since create: descents ended at a proven node, nodes that became proven wins, proven losses,
+        answers taken from a proof (hive_search_solver_stats)."""
+        return self._read(self.L.hive_search_solver_stats, 4)
 
     def node_values(self, game):
         """float32[n]: the value every node of game `game`'s tree was created with, in export_tree's node order
@@ -478,10 +524,13 @@ class ArenaSearch(TreeSearch):
     searched as without it, bit for bit.  One handle holds one parameter set: two dicts must be equal.
     gumbel_interior_a / gumbel_interior_b: that side's Gumbel searches also select below the root by the Gumbel rule
     (TreeSearch, gumbel_interior); a side with it must have gumbel_*.  gumbel_a=True, gumbel_b=True, gumbel_interior_a=True
-    is full Gumbel against root-only Gumbel on one handle."""
+    is full Gumbel against root-only Gumbel on one handle.
+    solver_a / solver_b: that side searches with proven wins and losses (TreeSearch, solver), by the same ownership rule;
+    not on a handle where either side has the Gumbel root."""
 
     def __init__(self, games, sims, evaluator_a, evaluator_b, a_white, device=None, slots=1, seed=0, plane_dtype=None,
-                 gumbel_a=None, gumbel_b=None, gumbel_interior_a=False, gumbel_interior_b=False, **options):
+                 gumbel_a=None, gumbel_b=None, gumbel_interior_a=False, gumbel_interior_b=False, solver_a=False,
+                 solver_b=False, **options):
         if options.get("reuse_store"):
             raise ValueError("ArenaSearch: reuse_store keeps evaluations by position alone, not by network")
         if options.get("keep_tree"):
@@ -492,12 +541,19 @@ class ArenaSearch(TreeSearch):
             raise ValueError("ArenaSearch: give the Gumbel root per side, gumbel_a / gumbel_b")
         if options.get("gumbel_interior"):
             raise ValueError("ArenaSearch: give the interior rule per side, gumbel_interior_a / gumbel_interior_b")
+        if options.get("solver"):
+            raise ValueError("ArenaSearch: give proven results per side, solver_a / solver_b")
         sides = [gumbel_options(x, slots, options.get("mode", PUCT)) for x in (gumbel_a, gumbel_b)]
         if sides[0] is not None and sides[1] is not None and sides[0] != sides[1]:
             raise ValueError("ArenaSearch: one handle holds one Gumbel parameter set; gumbel_a and gumbel_b differ")
         interior = (gumbel_interior_options(gumbel_interior_a, sides[0]), gumbel_interior_options(gumbel_interior_b, sides[1]))
+        # (one handle: a side with proven results cannot meet a side with the Gumbel root)
+        solver = tuple(solver_options(x, options.get("mode", PUCT), sides[0] or sides[1]) for x in (solver_a, solver_b))
         super().__init__(games, sims, evaluator_a, device, slots, seed, plane_dtype,
-                         **dict(options, gumbel=sides[0] or sides[1]))
+                         **dict(options, gumbel=sides[0] or sides[1], solver=solver[0] or solver[1]))
+        self._solver_sides = solver
+        if solver[0] != solver[1]:                              # one side only: rewritten in place from the ownership rule
+            self.set_solver(True, torch.zeros((games,), dtype=torch.int8, device=self.device))
         self._gumbel_sides = (sides[0] is not None, sides[1] is not None)
         if self._gumbel_sides[0] != self._gumbel_sides[1]:      # one side only: the mask is rewritten in place at every search
             self.set_gumbel_where(torch.zeros((games,), dtype=torch.int8, device=self.device))
@@ -530,13 +586,15 @@ class ArenaSearch(TreeSearch):
 
     def search(self, root_boards, root_hist, active=None, selfplay=False, keep_root_planes=False, budgets=None, quiet=None):
         self._roots = root_boards
-        if self._gumbel_where is not None or self._gumbel_interior_where is not None:
+        if self._gumbel_where is not None or self._gumbel_interior_where is not None or self._solver_where is not None:
             # the owner of the search of game g (hive_arena_budget_launch's rule): A iff a_white[g] == (root turn is odd)
             a_owns = (self.a_white != 0) == ((root_boards[:, 33] & 1) != 0)
             if self._gumbel_where is not None:
                 self._gumbel_where.copy_(a_owns if self._gumbel_sides[0] else ~a_owns)
             if self._gumbel_interior_where is not None:
                 self._gumbel_interior_where.copy_(a_owns if self._interior_sides[0] else ~a_owns)
+            if self._solver_where is not None:
+                self._solver_where.copy_(a_owns if self._solver_sides[0] else ~a_owns)
         out = super().search(root_boards, root_hist, active, selfplay, keep_root_planes, budgets=budgets, quiet=quiet)
         torch.sum(self.rows, 0, keepdim=True, out=self.evals_run)
         return out
@@ -621,7 +679,10 @@ class SelfPlay:
     move is the root's argmax(g + logit + sigma(q)) -- the opening resampling of turns <= 6 does not apply, the Gumbel draw is
     the exploration -- and the recorded policy is the improved policy, through the same record route.  In lock step, with
     playout_cap (a quiet fast ply has g = 0 and is deterministic) and with rolling; one slot, no keep_tree.
-    {"gumbel": True, "gumbel_interior": True} adds the Gumbel rule below the root (TreeSearch, gumbel_interior)."""
+    {"gumbel": True, "gumbel_interior": True} adds the Gumbel rule below the root (TreeSearch, gumbel_interior).
+    {"solver": True}: proven wins and losses below the root (TreeSearch, solver): a game whose tree holds the finishing move
+    plays it; the recorded policy stays the visit distribution.  In lock step, with playout_cap, rolling and keep_tree; not
+    with gumbel."""
 
     def __init__(self, games, sims, evaluator, device=None, slots=1, seed=0, plane_dtype=None,
                  keep_records=True, game_ids=None, max_finished_kept=1024, report_every=0, log=print, packed_records=False,

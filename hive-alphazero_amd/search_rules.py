@@ -201,3 +201,68 @@ def gumbel_interior_choice(p, n, w, v_node, c_visit=GUMBEL_DEFAULTS["c_visit"], 
     _, improved = gumbel_improved_policy(p, n, w, v_node, c_visit, c_scale)
     score = improved - n / (1.0 + float(n.sum()))
     return int(np.argmax(score)), score
+
+
+# ---- Proven wins and losses below the root (include/hive_search.h, hive_search_set_solver): the numpy statements, no GPU
+# (imported by name: mcts.py re-exports them next to the names of __all__)
+def solver_edge_status(child_status):
+    """The status of an edge whose child has status `child_status` (int or int array), from the mover at the edge's parent:
+    -sign(c) * (|c| + 1), and 0 for an unknown child."""
+    c = np.asarray(child_status, dtype=np.int64)
+    out = -np.sign(c) * (np.abs(c) + 1)
+    return int(out) if out.ndim == 0 else out
+
+
+def solver_node_status(edge_status):
+    """The status of a node from the statuses of ALL its edges: the smallest positive one if any edge wins (the fastest win),
+    else -max|e| if every edge loses (the longest resistance), else 0.  An edge that is not expanded holds 0 and blocks a
+    loss proof; the pass edge is an edge like any other."""
+    e = np.asarray(edge_status, dtype=np.int64).reshape(-1)
+    if (e > 0).any():
+        return int(e[e > 0].min())
+    if e.size and (e < 0).all():
+        return -int(np.abs(e).max())
+    return 0
+
+
+def solver_holds(status, turn, cap):
+    """Does a status (node or edge; int or int array) hold on a path whose current turn is `turn`?  Iff it is not 0 and the
+    finished position lies within the length cap: turn + |status| - 1 <= cap."""
+    x = np.asarray(status, dtype=np.int64)
+    out = (x != 0) & (int(turn) + np.abs(x) - 1 <= int(cap))
+    return bool(out) if out.ndim == 0 else out
+
+
+def solver_answer(edge_status, n, turn, cap):
+    """(edge, allowed bool[ne]): the answer at a root at turn `turn` whose edges hold `edge_status` and the visits n.
+    edge >= 0: the move comes from a proof -- the root's status (solver_node_status of its edges) holds and is positive:
+    the smallest positive status that holds; or negative: the largest |e|; ties to more visits, then to the lower edge.
+    edge = -1: no proof; the caller's own choice runs over the edges with allowed[e] -- every edge but those whose status
+    holds and is negative, unless every edge is such."""
+    e = np.asarray(edge_status, dtype=np.int64).reshape(-1)
+    n = np.asarray(n, dtype=np.int64).reshape(-1)
+    holds = solver_holds(e, turn, cap) if e.size else np.zeros(0, dtype=bool)
+    banned = holds & (e < 0)
+    allowed = ~banned if not banned.all() else np.ones(e.size, dtype=bool)
+    root = solver_node_status(e)
+    if not solver_holds(root, turn, cap):
+        return -1, allowed
+    cand = np.flatnonzero(holds & ((e > 0) == (root > 0)))
+    speed = -e[cand] if root > 0 else np.abs(e[cand])      # larger is better: the fastest win, the longest resistance
+    order = sorted(zip((-speed).tolist(), (-n[cand]).tolist(), cand.tolist()))
+    return int(order[0][2]), allowed
+
+
+def solver_options(solver, mode=PUCT, gumbel=None):
+    """TreeSearch's `solver` argument checked (no GPU): True iff proven wins and losses are on.  Refused, as
+    hive_search_set_solver refuses them: UCT mode, and together with the Gumbel root (its halving schedule counts root visits,
+    and a proven root ends descents at depth 0)."""
+    if not solver:
+        return False
+    if solver is not True and solver != 1:
+        raise ValueError("solver takes True or False")
+    if mode == UCT:
+        raise ValueError("solver: proven results have no UCT form (PUCT mode only)")
+    if gumbel:
+        raise ValueError("solver: not with the Gumbel root (its halving schedule counts root visits)")
+    return True

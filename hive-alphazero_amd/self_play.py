@@ -154,7 +154,7 @@ class SelfPlayWorker:
     hand-over carries the `full` key of a capped batch, the reference's JSON rows have no room for it, and a rolling child
     hands over games one by one as they end.  search_options (e.g. {"gumbel": True}: the Gumbel root of mcts.TreeSearch) go
     to every child's SelfPlay(search_options=...) unchanged; {"gumbel": True, "gumbel_interior": True} adds the Gumbel rule
-    below the root."""
+    below the root; {"solver": True} searches with proven wins and losses below the root."""
 
     def __init__(self, total_games, games_per_gpu=1024, sims=50, gpus=None, seed=0, net_seed=0, checkpoint=None, slots=1,
                  datapath="../dataSelf", games_per_file=100, report_every=10, worker=_game_worker, log=print, row_format="json",
@@ -184,6 +184,8 @@ class SelfPlayWorker:
                 search_options.get("gumbel_interior"),
                 search_rules.gumbel_options(search_options.get("gumbel"), int(slots),
                                             keep_tree=bool(search_options.get("keep_tree"))))
+            search_rules.solver_options(search_options.get("solver"), search_options.get("mode", search_rules.PUCT),
+                                        search_options.get("gumbel"))
             search_rules.rolling_options(self.cfg["rolling"], search_options, int(sims), int(slots), self.cfg["playout_cap"])
         if gpus is None:
             import torch

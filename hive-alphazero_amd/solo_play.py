@@ -25,7 +25,8 @@ import numpy as np
 
 from . import config
 from .config import ACTION_SPACE, MAX_GAME_LENGTH, PIECE_BLACK, PIECE_WHITE
-from .search_rules import GUMBEL_DEFAULTS, gumbel_considered_visits, gumbel_improved_policy, gumbel_interior_choice
+from .search_rules import (GUMBEL_DEFAULTS, gumbel_considered_visits, gumbel_improved_policy, gumbel_interior_choice,
+                           solver_answer, solver_edge_status, solver_holds, solver_node_status)
 
 # woker/solo_play.py:23-30 (module-level knobs, same names so callers can override them the same way)
 simulation_num_per_move = 100
@@ -42,7 +43,7 @@ _DRAW = 5          # sentinel a drawn / length-capped line returns (solo_play.py
 class _Entry:
     """One position of the transposition table: raw network priors until its first selection, then
     per-edge arrays in legal-move order."""
-    __slots__ = ("raw_p", "moves", "n", "w", "p", "sum_n", "v")
+    __slots__ = ("raw_p", "moves", "n", "w", "p", "sum_n", "v", "status", "es")
 
     def __init__(self, raw_p, v=0.0):
         self.raw_p = raw_p
@@ -50,6 +51,8 @@ class _Entry:
         self.moves = None
         self.n = self.w = self.p = None
         self.sum_n = 0
+        self.status = 0                # proven result from the side to move here (HivePlayer.solver), 0 = unknown
+        self.es = None                 # per-edge statuses from the mover's side, with the other edge arrays
 
     def open_edges(self, legal):
         """First selection at this position: priors of the legal moves, renormalised with the reference's
@@ -60,6 +63,7 @@ class _Entry:
         self.p = prior / running[-1]
         self.n = np.zeros(len(legal), dtype=np.int64)
         self.w = np.zeros(len(legal), dtype=np.float64)
+        self.es = np.zeros(len(legal), dtype=np.int64)
         self.raw_p = None
 
     def q(self):
@@ -128,6 +132,7 @@ class HivePlayer:
         self.max_depth = None
         self._table = {}
         self._locks = defaultdict(Lock)
+        self.solver_stats = [0, 0, 0, 0]
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -180,6 +185,14 @@ class HivePlayer:
     # too, and gumbel_interior_min_gap holds theirs alone.
     gumbel = None
 
+    # True: proven wins and losses below the root, the sequential statement of hive_search_set_solver (the rule:
+    # include/hive_search.h).  Every table entry keeps a status and per-edge statuses, updated along the path after the
+    # reference's backup; a descent ends at an entry whose status holds, moves proven to lose are left out of PUCT and of the
+    # answer, and a proven root answers from the proof.  The policy and the visit total are the reference's.  After action():
+    # solver_stats = [descents ended at a proven entry, entries that became proven wins, proven losses, answers from a proof]
+    # since the player was made.  Not with `gumbel`.  False: the reference.
+    solver = False
+
     def action(self, env, non_queue=True):
         if self.keep_tree:
             self.keep_reachable(env)
@@ -187,6 +200,9 @@ class HivePlayer:
             self.reset()
         self.max_depth = env.state.turn
         self.main_key_state = env.state_key
+        if self.solver:
+            if self.gumbel is not None or (self.none_queue and SEARCH_THREADS > 1):
+                raise ValueError("HivePlayer.solver: sequential PUCT search only, not with gumbel")
         if self.gumbel is not None:
             if self.keep_tree or (self.none_queue and SEARCH_THREADS > 1):
                 raise ValueError("HivePlayer.gumbel: sequential search without kept trees only")
@@ -197,7 +213,18 @@ class HivePlayer:
         policy, visits = self.calc_policy(env)
         if self.gumbel is not None:
             return self._gumbel_move(env), [list(policy), visits]
-        probs = self.apply_temperature(policy, int(env.state.turn + 1) / 2)
+        choice = policy
+        if self.solver:
+            entry = self._table[env.state_key]
+            if entry.moves is not None:
+                edge, allowed = solver_answer(entry.es, entry.n, env.state.turn, MAX_GAME_LENGTH)
+                if edge >= 0:
+                    self.solver_stats[3] += 1
+                    return int(entry.moves[edge]), [list(policy), visits]
+                if not allowed.all():                        # the moves proven to lose leave the choice, not the policy
+                    choice = np.array(policy, dtype=np.float64)
+                    choice[np.asarray(entry.moves)[~allowed]] = -1.0
+        probs = self.apply_temperature(choice, int(env.state.turn + 1) / 2)
         move = int(np.random.choice(range(ACTION_SPACE), p=probs))
         return move, [list(policy), visits]
 
@@ -216,11 +243,14 @@ class HivePlayer:
         path = []                      # (entry, edge index) from the root down
         outcome = None
         depth = 0
+        proven = 0                     # solver: the status of the position where the path ends
         if self.gumbel is not None and is_root_node:
             self._cur_sim, self._sim = self._sim, self._sim + 1       # simulations of a search are numbered 0, 1, ...
         while True:
             outcome = _terminal_value(env)
             if outcome is not None:
+                if self.solver and outcome != _DRAW and env.game_is_over():
+                    proven = int(outcome)                    # only a finished game with a winner proves anything
                 break
             key = env.state_key
             with self._locks[key]:
@@ -231,6 +261,11 @@ class HivePlayer:
                     outcome = leaf_v
                     if self.gumbel is not None and is_root_node and depth == 0:
                         self._root_v = float(np.asarray(leaf_v).reshape(-1)[0])      # completes the unvisited root edges
+                    break
+                if self.solver and solver_holds(entry.status, env.state.turn, MAX_GAME_LENGTH):
+                    proven = entry.status                    # a proven position ends the descent like a finished game
+                    outcome = 1 if proven > 0 else -1
+                    self.solver_stats[0] += 1
                     break
                 edge, move = self._select(entry, env, is_root_node and depth == 0)
                 entry.sum_n += virtual_loss                 # virtual loss (solo_play.py:205-208)
@@ -251,6 +286,22 @@ class HivePlayer:
                 entry.n[edge] += -virtual_loss + 1
                 entry.w[edge] += virtual_loss + seen
             value = _DRAW if drawn else seen
+        if proven:
+            # proven results travel up this path, deepest edge first: the edge takes the child's status seen from the mover,
+            # the entry is decided by all of its edges
+            result = value
+            for key, entry, edge in reversed(path):
+                if abs(proven) >= 127:
+                    break
+                with self._locks[key]:
+                    entry.es[edge] = solver_edge_status(proven)
+                    status = solver_node_status(entry.es)
+                    if entry.status == 0 and status != 0:
+                        self.solver_stats[1 if status > 0 else 2] += 1
+                    entry.status = proven = status
+                if proven == 0:
+                    break
+            return result
         return value
 
     def expand_and_evaluate(self, env):
@@ -286,6 +337,7 @@ class HivePlayer:
                 entry.moves, entry.raw_p = [-1], None
                 entry.n, entry.w = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.float64)
                 entry.p = np.zeros(1, dtype=np.float64)
+                entry.es = np.zeros(1, dtype=np.int64)
             return 0, -1
         if entry.moves is None:
             entry.open_edges(legal)
@@ -298,6 +350,10 @@ class HivePlayer:
             noise = np.random.dirichlet([dirichlet_alpha] * len(entry.moves))
             prior = (1 - noise_eps) * prior + noise_eps * noise
         score = entry.q() + c_puct * prior * np.sqrt(entry.sum_n + 1) / (1 + entry.n)
+        if self.solver:
+            banned = solver_holds(entry.es, env.state.turn, MAX_GAME_LENGTH) & (entry.es < 0)
+            if banned.any() and not banned.all():            # moves proven to lose are left out unless every move is one
+                score = np.where(banned, -np.inf, score)
         edge = int(np.argmax(score))
         return edge, entry.moves[edge]
 

@@ -301,6 +301,64 @@ int hive_search_gumbel_fallbacks(HiveSearch *s, int32_t *count);
  * root's `where`, and every refusal of hive_search_set_gumbel. */
 int hive_search_set_gumbel_interior(HiveSearch *s, int on, const int8_t *where);
 
+/* ---- Proven wins and losses below the root (the MCTS-Solver rule: Winands, Bjornsson, Saito, "Monte-Carlo Tree Search
+ * Solver", 2008).  Opt-in, PUCT mode, off by default; a game outside `where` is searched and answered bit for bit as without
+ * the call.
+ *
+ * Status is a signed int8, 0 = unknown.  A NODE status s is taken from the side to move at the node: s > 0 that side wins,
+ * s < 0 it loses, and |s| - 1 is the number of plies to the finished position under the proof.  An EDGE status e is taken
+ * from the mover at the edge's parent, with the same meaning for the move.
+ * What proves: only a finished game with a winner.  Such a node gets s = +1 when the side to move there is the winner, else
+ * -1 (the winner rule that sets tv).  A finished game without a winner (both queens surrounded: the draw sentinel), the
+ * length cap and a position without legal moves prove nothing: they keep status 0 and are averaged exactly as without the
+ * option.
+ * Propagation, in hive_search_backup after the value backup and only along the path of this simulation: c = the status of
+ * the node where the path ended (a new or known finished game, or a node at which the descent stopped because it is proven).
+ * While c != 0 and |c| < 127, for d = plen-1 .. 0 with P = path_node[d], k = path_edge[d]:
+ *   e_status[P][k] = -sign(c) * (|c| + 1)
+ *   s_P = the smallest positive e over all ne edges of P if any is positive (the fastest win), else -max|e| if every edge is
+ *         negative (the longest resistance), else 0;  node_status[P] = s_P;  c = s_P
+ * No early stop on "was already proven": the upper edges of this path may not know yet.  The pass edge is an edge like any
+ * other.  An edge that was never backed up through an expanded child holds 0 and so blocks a loss proof.  Edge statuses are
+ * written here and nowhere else: a position shared through the transposition table may be proven through one parent while
+ * another parent's edge still says 0; that parent learns it when a descent next passes through it.  Statuses are path-local
+ * until then, and every step is one the sequential player (solo_play.py, HivePlayer.solver) restates.
+ * The length cap: the position key holds no turn number, so a node may be reached at a later turn than it was proven at.  A
+ * status x HOLDS on a path whose current turn is T iff x != 0 and T + |x| - 1 <= max_game_length.  A status that does not
+ * hold is treated as 0 by the two rules below; it stays stored.
+ * Select: after the finished-game and the length-cap checks of hive_search_select, a node whose status holds ends the descent
+ * (the root too: path length 0).  Such a descent is a known finished game: no leaf row, hive_search_leaf_need answers 0, the
+ * value backed up is +1.0f or -1.0f by the sign, and it counts in bucket [3] of hive_search_leaf_histogram.  At a node that is
+ * passed through, edges whose status holds and is negative are left out of the PUCT argmax unless all edges are such.  Noise,
+ * virtual loss, collisions and pool exhaustion are unchanged.
+ * Answer (hive_search_policy / _policy_where) at root turn T: root status holds and is > 0: the edge with the smallest positive
+ * status that holds, ties to more visits, then to the lower edge; holds and is < 0: the edge with the largest |e|, same ties;
+ * otherwise edges whose status holds and is negative are left out of the existing choice (argmax, the "every W negative ->
+ * priors" fallback, the selfplay resampling) unless every edge is such.  A root with a holding status is not resampled.  The
+ * policy row and sum_n are unchanged: the visit distribution as ever (a proven root ends descents at depth 0, so it collects
+ * no further visits).
+ * Not claimed: draws and the cap prove nothing; it is not combined with the Gumbel root (its halving schedule counts root
+ * visits): HIVE_E_ARG from this call while hive_search_set_gumbel is on and from that call while this is on; HIVE_E_ARG in UCT
+ * mode (here, and from hive_search_set_params to UCT while on).  Composes with slots > 1 (backups run slot after slot),
+ * budgets, per-game clocks and hive_search_advance_roots, which moves both status arrays with the kept nodes and edges.
+ *
+ * on != 0 switches it on for the games with where[g] != 0 (DEVICE int8[games] the caller owns and the handle keeps the pointer
+ * of; NULL = every game).  The first such call allocates node_status int8[games][max_nodes] and e_status
+ * int8[games][max_nodes][HIVE_EDGE_CAP], and their twins in the second node pool, zeroed; from then on every node creation
+ * writes its status and zeroes its edges' (nodes created earlier read 0). */
+int hive_search_set_solver(HiveSearch *s, int on, const int8_t *where);
+
+/* One game's statuses in hive_search_export_tree's layout: node = int8[max_nodes], edge = int8[max_nodes][HIVE_EDGE_CAP]
+ * (either may be NULL).  Zeros before the first hive_search_set_solver. */
+int hive_search_node_status(HiveSearch *s, int game, int8_t *node, int8_t *edge);
+
+/* int8[games]: the stored status of node 0 (0 for a game without a tree). */
+int hive_search_root_status(HiveSearch *s, int8_t *status);
+
+/* int32[games][4] since create: [0] descents ended at a proven node, [1] nodes that became proven wins and [2] proven losses
+ * by propagation (status 0 before), [3] answers taken from a proof. */
+int hive_search_solver_stats(HiveSearch *s, int32_t *out);
+
 /* The search's own noise generator, exposed for statistical tests: draw d (= 0 .. draws-1) is what the root of game id
  * `first_game + d` would get at (turn, sim 0, slot 0): eta ~ Dirichlet(alpha) over k <= HIVE_EDGE_CAP edges
  * (solo_play.py:322-323, np.random.dirichlet).  out = float[draws][k]; prior = float[k] or NULL:

@@ -12,7 +12,8 @@ builds B from A's weights: the match then measures what the extra simulations ar
 adds the result as a section to a profile file.
 
 --gumbel-a / --gumbel-b: that side searches with the Gumbel root (Arena(gumbel_a=, gumbel_b=); m = 16, c_visit = 50,
-c_scale = 1)."""
+c_scale = 1).  --solver-a / --solver-b: that side searches with proven wins and losses below the root
+(Arena(solver_a=, solver_b=)); not together with a Gumbel side."""
 import argparse
 import json
 import os
@@ -119,6 +120,8 @@ def main():
     ap.add_argument("--gumbel-interior-a", action="store_true",
                     help="A's Gumbel search also selects below the root by the Gumbel rule (needs --gumbel-a)")
     ap.add_argument("--gumbel-interior-b", action="store_true", help="the same for B (needs --gumbel-b)")
+    ap.add_argument("--solver-a", action="store_true", help="A searches with proven wins and losses below the root")
+    ap.add_argument("--solver-b", action="store_true", help="the same for B")
     ap.add_argument("--append", default=None, metavar="FILE", help="append the result to this profile file")
     args = ap.parse_args()
     if len(args.checkpoints) not in (0, 2):
@@ -134,7 +137,7 @@ def main():
     ar = Arena(A, B, pairs=args.pairs, sims=args.sims, slots=args.slots, games_in_flight=args.games_in_flight, seed=args.seed,
                opening_turns=args.opening_turns, noise_eps=args.noise_eps, keep_moves=False, sims_b=args.sims_b,
                gumbel_a=args.gumbel_a or None, gumbel_b=args.gumbel_b or None, gumbel_interior_a=args.gumbel_interior_a,
-               gumbel_interior_b=args.gumbel_interior_b)
+               gumbel_interior_b=args.gumbel_interior_b, solver_a=args.solver_a, solver_b=args.solver_b)
     res, seconds = play(ar)
     rows = ar.rows_evaluated()
     assert ar.illegal_count() == 0
@@ -144,7 +147,8 @@ def main():
     d.update(passes=res.passes(args.min_score), passes_ci=res.passes_ci(), seconds=seconds,
              games_per_min=60.0 * res.games / seconds, rows_a=rows[0], rows_b=rows[1], sims=args.sims, seed=args.seed,
              sims_b=args.sims_b if args.sims_b is not None else args.sims, gumbel_a=args.gumbel_a, gumbel_b=args.gumbel_b,
-             gumbel_interior_a=args.gumbel_interior_a, gumbel_interior_b=args.gumbel_interior_b)
+             gumbel_interior_a=args.gumbel_interior_a, gumbel_interior_b=args.gumbel_interior_b, solver_a=args.solver_a,
+             solver_b=args.solver_b)
     print(json.dumps(d))
     if args.append:
         with open(args.append, "a") as f:
@@ -154,12 +158,15 @@ def main():
                        if args.gumbel_a or args.gumbel_b else "")
                     + (", also below the root for " + " and ".join(n for n, on in (("A", args.gumbel_interior_a),
                                                                                   ("B", args.gumbel_interior_b)) if on)
-                       if args.gumbel_interior_a or args.gumbel_interior_b else "") + "\n\n"
+                       if args.gumbel_interior_a or args.gumbel_interior_b else "")
+                    + (", proven wins and losses for " + " and ".join(n for n, on in (("A", args.solver_a), ("B", args.solver_b)) if on)
+                       if args.solver_a or args.solver_b else "") + "\n\n"
                     f"`python tools/arena.py --pairs {args.pairs} --sims {args.sims} --sims-b {d['sims_b']} --seed {args.seed} "
                     f"--noise-eps {args.noise_eps} --dtype {args.dtype}" + (" --same-weights" if args.same_weights else "")
                     + (" --gumbel-a" if args.gumbel_a else "") + (" --gumbel-b" if args.gumbel_b else "")
                     + (" --gumbel-interior-a" if args.gumbel_interior_a else "")
-                    + (" --gumbel-interior-b" if args.gumbel_interior_b else "") + "`\n\n"
+                    + (" --gumbel-interior-b" if args.gumbel_interior_b else "")
+                    + (" --solver-a" if args.solver_a else "") + (" --solver-b" if args.solver_b else "") + "`\n\n"
                     f"A searches {args.sims} simulations per move, B {d['sims_b']}.  {res!r}\n\n"
                     f"Score of A {res.score:.3f}, 95 % interval [{res.score_ci95[0]:.3f}, {res.score_ci95[1]:.3f}] over "
                     f"{len(res.pair_scores)} pairs ({res.games} games in {seconds:.1f} s); rows through a tower: A {rows[0]}, "

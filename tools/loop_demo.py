@@ -20,7 +20,10 @@ search then runs max(FULL, FAST) simulations and the trainer sees the rows flagg
 the longest search of the batch; the same games, bit for bit, in fewer rounds when the plies' searches differ in length.
 
 --gumbel (default off): the Gumbel root with sequential halving; --gumbel-interior adds the Gumbel rule below the root (it
-requires --gumbel)."""
+requires --gumbel).
+
+--solver (default off): proven wins and losses below the root, mcts.SelfPlay(search_options={"solver": True}); not with
+--gumbel."""
 import argparse, os, sys, time, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hive_alphazero_amd import mcts, records
@@ -33,9 +36,12 @@ ap.add_argument("--playout-cap", default=None, metavar="FULL,FAST,P", help="full
 ap.add_argument("--rolling", action="store_true", help="every game moves when its own search is done (same games, fewer rounds under a playout cap)")
 ap.add_argument("--gumbel", action="store_true", help="Gumbel root with sequential halving; the records hold the improved policy")
 ap.add_argument("--gumbel-interior", action="store_true", help="with --gumbel: the Gumbel rule also selects below the root")
+ap.add_argument("--solver", action="store_true", help="proven wins and losses below the root (not with --gumbel)")
 opts = ap.parse_args()
 if opts.gumbel_interior and not opts.gumbel:
     ap.error("--gumbel-interior requires --gumbel")
+if opts.solver and opts.gumbel:
+    ap.error("--solver is not combined with --gumbel")
 gate, window = opts.gate, opts.replay
 cap = None
 if opts.playout_cap:
@@ -54,7 +60,8 @@ for rnd in range(rounds):
     net.eval()
     sp = mcts.SelfPlay(games, sims, evaluator, seed=100 + rnd, game_ids=range(rnd * games, (rnd + 1) * games),
                        packed_records=True, max_finished_kept=2 * games, playout_cap=cap, rolling=opts.rolling or None,
-                       search_options={"gumbel": True, "gumbel_interior": opts.gumbel_interior} if opts.gumbel else None)
+                       search_options={"gumbel": True, "gumbel_interior": opts.gumbel_interior} if opts.gumbel
+                       else ({"solver": True} if opts.solver else None))
     t0 = time.perf_counter()
     batches = []
     while sp.running() and sp.plies < (80 * sims if opts.rolling else 80):      # (rolling: plies counts turn-overs)
